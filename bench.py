@@ -1,7 +1,14 @@
 """Headline benchmark: int8 voltage Gsamples/s through the fused MI355X beamformer (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4] [--no-cpu-baseline] [--no-pmc]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-pmc] [--no-secondary] [--no-stream] [--no-ceiling] [--no-rocprof]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the K steps, writes the last
+timed step's beams if `--dump-outputs DIR` is given (float32 .npy, a fixed seeded sample of a large output; the
+synthetic input is seeded, so two builds can be compared output for output) and prints the line.  Everything else
+below -- the int8 contract check, `ceiling`, every `secondary`, the rocprofv3 re-run, the PMC `traffic` and
+`cpu_baseline` -- is measured only with `--full`.
 
 `--gpus N` alone starts the N ranks itself (N child processes of this script, one per GPU, RANK / WORLD_SIZE /
 MASTER_* set; the parent never touches a GPU); under an external launcher `--gpus` must equal WORLD_SIZE.
@@ -70,6 +77,13 @@ def parse(argv=None):
                         "itself; under torch.distributed.run it must equal WORLD_SIZE (default: WORLD_SIZE, else 1)")
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline's timed steps: the int8 contract check, the stream "
+                        "ceiling, the secondary workloads, the streaming secondary, the rocprofv3 re-run, the PMC "
+                        "passes and the CPU baseline (each still switched off by its --no-... option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the beams of the last timed step to DIR/beams.npy (float32; a "
+                        "fixed seeded sample of a large output; DIR/beams_rank<r>.npy per rank at N > 1)")
     p.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg3")
     p.add_argument("--output", choices=("int8", "f32"), default="int8",
                    help="int8 requantised beams (bit-exact integer path, default) or float32 beams")
@@ -111,6 +125,8 @@ def parse(argv=None):
     if a.out_int8:
         a.output = "int8"
     a.out_int8 = a.output == "int8"
+    if not a.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        a.no_cpu_baseline = a.no_pmc = a.no_secondary = a.no_stream = a.no_ceiling = a.no_rocprof = True
     return a
 
 
@@ -421,6 +437,26 @@ def contract_check(args, dist, wl, r):
             "max_abs_lsb": int(diff.max())}
 
 
+DUMP_MAX_VALUES = 1 << 23  # 32 MiB of float32 over all ranks' files together
+DUMP_SEED = 20
+
+
+def dump_outputs(args, dist, r):
+    """--dump-outputs DIR: the beams the last timed step wrote (the `outData` a caller of the fused operator reads
+    back), as float32 in DIR/beams.npy (DIR/beams_rank<r>.npy at N > 1).  The ranks share DUMP_MAX_VALUES values: a
+    rank's output of more than DUMP_MAX_VALUES // N values is sampled at that many flat positions, drawn once from a
+    fixed seed and sorted, so two runs with the same arguments write the same positions of the same inputs' beams."""
+    import numpy as np
+    ops = r["ops"]
+    y = ops[(max(args.steps, 1) - 1) % len(ops)].buffer("outData").get(args.queue).reshape(-1)
+    cap = DUMP_MAX_VALUES // dist.world
+    if y.size > cap:
+        y = y[np.sort(np.random.default_rng(DUMP_SEED).integers(0, y.size, cap))]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    name = "beams.npy" if dist.world == 1 else f"beams_rank{dist.rank}.npy"
+    np.save(os.path.join(args.dump_outputs, name), y.astype(np.float32))
+
+
 def stream_ceiling(args, in_bytes, out_bytes):
     """The same traffic mix (in_bytes read, out_bytes written) as plain streaming kernels from the stream-ceiling
     library (build/libbf_stream.so, tools/stream_ceiling.hip: 16-byte lanes, plain / non-temporal loads and stores,
@@ -693,10 +729,10 @@ def rocprof_check(args, n_secondary):
     out = args.prof_out or tempfile.mkdtemp(prefix="bfprof_", dir=os.environ.get("TMPDIR", "/tmp"))
     os.makedirs(out, exist_ok=True)
     cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "bench", "--", sys.executable,
-           os.path.abspath(__file__), "--prof-child", "--workload", args.workload, "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--settle-ms", str(args.settle_ms), "--output", args.output,
-           "--int8-contract", args.int8_contract, "--coeff-table", args.coeff_table, "--no-pmc", "--no-cpu-baseline",
-           "--no-ceiling", "--no-stream"]
+           os.path.abspath(__file__), "--prof-child", "--full", "--workload", args.workload,
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--settle-ms", str(args.settle_ms),
+           "--output", args.output, "--int8-contract", args.int8_contract, "--coeff-table", args.coeff_table,
+           "--no-pmc", "--no-cpu-baseline", "--no-ceiling", "--no-stream"]
     cmd += (["--unsigned"] if args.unsigned else []) + (["--no-secondary"] if n_secondary == 0 else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     files = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
@@ -922,7 +958,10 @@ def main():
     }
     if dist.group:
         line["per_rank_avg_launch_us"] = dist.group.gather_json(round(r["kernel_s"] * 1e6, 2))
-    if dist.rank == 0 and dist.world == 1 and args.out_int8 and args.int8_contract == "q14" and not args.prof_child:
+    if args.dump_outputs:
+        dump_outputs(args, dist, r)
+    if args.full and dist.rank == 0 and dist.world == 1 and args.out_int8 and args.int8_contract == "q14" \
+            and not args.prof_child:
         line["int8_contract_check"] = contract_check(args, dist, wl, r)
     r.pop("ops")
     if dist.rank == 0 and dist.world == 1 and not args.no_ceiling:

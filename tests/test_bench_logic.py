@@ -138,6 +138,69 @@ def test_resolve_world_launch_and_mismatch():
         bench.resolve_world(bench.parse(["--gpus", "0"]), env={})
 
 
+EXTRAS = ("no_cpu_baseline", "no_pmc", "no_secondary", "no_stream", "no_ceiling", "no_rocprof")
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full every measurement beside the timed steps is off; --full turns them on, each still switched off
+    by its own --no-... option."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert all(getattr(a, k) for k in EXTRAS)
+    a = bench.parse(["--full"])
+    assert a.full and not any(getattr(a, k) for k in EXTRAS)
+    a = bench.parse(["--full", "--no-pmc", "--dump-outputs", "d"])
+    assert a.dump_outputs == "d" and [k for k in EXTRAS if getattr(a, k)] == ["no_pmc"]
+
+
+class _FakeOp:
+    def __init__(self, y):
+        self.y = y
+
+    def buffer(self, name):
+        assert name == "outData"
+        return self
+
+    def get(self, queue):
+        return self.y
+
+
+def test_dump_outputs_last_step_sampled_and_repeatable(tmp_path):
+    """--dump-outputs writes the output of the buffer set the last timed step ran on, as float32; a large output is
+    sampled at the same seeded positions every time; at N > 1 every rank writes its own file."""
+    import argparse
+
+    import numpy as np
+    rng = np.random.default_rng(3)
+    small = [rng.integers(-128, 128, (2, 3, 5), dtype=np.int8) for _ in range(2)]
+    one = argparse.Namespace(world=1, rank=0)
+    for steps, last in ((4, 1), (5, 0), (1, 0)):
+        args = argparse.Namespace(steps=steps, queue=None, dump_outputs=str(tmp_path / f"s{steps}"))
+        bench.dump_outputs(args, one, {"ops": [_FakeOp(y) for y in small]})
+        got = np.load(tmp_path / f"s{steps}" / "beams.npy")
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, small[last].reshape(-1))
+    n = bench.DUMP_MAX_VALUES + 12345
+    big = rng.standard_normal(n).astype(np.float32)
+    for d in ("a", "b"):
+        args = argparse.Namespace(steps=1, queue=None, dump_outputs=str(tmp_path / d))
+        bench.dump_outputs(args, one, {"ops": [_FakeOp(big)]})
+    a, b = (np.load(tmp_path / d / "beams.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.size == bench.DUMP_MAX_VALUES
+    np.testing.assert_array_equal(a, b)
+    assert np.isin(a[:1000], big).all() and len(np.unique(a)) > a.size // 2  # values of the output, spread over it
+    # every rank of a world-N run writes its own file; together they stay within 64 MB
+    for world in (1, 2, 3, 8):
+        d = tmp_path / f"w{world}"
+        args = argparse.Namespace(steps=1, queue=None, dump_outputs=str(d))
+        for rank in range(world):
+            bench.dump_outputs(args, argparse.Namespace(world=world, rank=rank), {"ops": [_FakeOp(big)]})
+        names = sorted(os.listdir(d))
+        assert names == (["beams.npy"] if world == 1 else [f"beams_rank{r}.npy" for r in range(world)])
+        assert sum(os.path.getsize(d / f) for f in names) <= 64e6
+        assert all(np.load(d / f).size == bench.DUMP_MAX_VALUES // world for f in names)
+
+
 def _run_bench(args, env_extra=None, timeout=120):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}

@@ -106,7 +106,8 @@ def test_bench_multi_rank_rehearsal(tmp_path):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "1", "--settle-ms", "0", "--scatter-backend", "host", "--workload", "cfg3", "--nbuf", "1"]
+           "--warmup", "1", "--settle-ms", "0", "--scatter-backend", "host", "--workload", "cfg3", "--nbuf", "1",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -127,7 +128,7 @@ def test_bench_gpus_two_without_launcher(tmp_path):
     its two ranks itself (both on this one GPU, host scatter backend since RCCL refuses two ranks on one device).
     Both ranks time their X-engine's shard and the config-4 secondaries; rank 0 prints the one line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--settle-ms", "0", "--scatter-backend", "host", "--workload", "cfg3", "--nbuf", "1"]
+           "--settle-ms", "0", "--scatter-backend", "host", "--workload", "cfg3", "--nbuf", "1", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -14,7 +14,7 @@ for s in $STAGES; do
   case $s in
     smoke)  timeout -k 10 300 python __graft_entry__.py > $OUT/smoke.log 2>&1 || { echo "smoke failed"; exit 1; } ;;
     pytest) timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -p no:cacheprovider ${PYTEST_K:+-k "$PYTEST_K"} ${PYTEST_ARGS} > $OUT/pytest_gpu.log 2>&1 || { echo "pytest failed"; tail -30 $OUT/pytest_gpu.log; exit 1; } ;;
-    bench)  timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; } ;;
+    bench)  timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; } ;;
     # the profiled run's own JSON line (stdout) is kept next to its rocprof summary: both come from one process
     diag)   env ${DIAG_ENV} DIAG_STREAMS=${DIAG_STREAMS:-0} timeout -k 10 300 python tools/diag_fused.py ${DIAG_SHAPE:-1 4096 256 256 64} > $OUT/diag.txt 2>&1 || { echo "diag failed"; tail -20 $OUT/diag.txt; exit 1; }; cat $OUT/diag.txt ;;
     ops)    timeout -k 10 400 python tools/bench_ops.py ${OPS_ARGS} > $OUT/ops.jsonl 2> $OUT/ops.err || { echo "ops failed"; tail -20 $OUT/ops.err; exit 1; }; cat $OUT/ops.jsonl ;;
