@@ -9,16 +9,16 @@ SRCS     := $(CSRC)/bf_runtime.cpp $(CSRC)/bf_coeff.hip $(CSRC)/bf_reorder.hip $
             $(CSRC)/bf_fused.hip $(CSRC)/bf_wide.hip $(CSRC)/bf_wide_i8.hip $(CSRC)/bf_q14table.hip $(CSRC)/bf_requant.hip \
             $(CSRC)/bf_study.hip $(CSRC)/bf_pipeline.cpp $(CSRC)/bf_comm.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
-HDRS     := $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/diag/*.inc) include/bf.h
+HDRS     := $(wildcard $(CSRC)/*.hpp) include/bf.h
 
-.PHONY: all clean diag cabi stream
+.PHONY: all clean cabi stream
 all: $(LIB) cabi
 
-# bench.py's stream ceiling (the box's best plain stream over a kernel's byte mix): a small library of its own, so the
-# GPU box needs no diagnostic build.
+# bench.py's stream ceiling (the box's best plain stream over a kernel's byte mix): a small measurement library of its
+# own, never linked into the product.
 STREAM_LIB := build/libbf_stream.so
 stream: $(STREAM_LIB)
-$(STREAM_LIB): tools/stream_ceiling.hip $(CSRC)/diag/stream_kernels.hpp
+$(STREAM_LIB): tools/stream_ceiling.hip tools/stream_kernels.hpp
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 
@@ -47,16 +47,3 @@ $(LIB): $(OBJS)
 
 clean:
 	rm -rf build $(LIB)
-
-# Diagnostic build (ablation variants + HBM stream kernel); used only by tools/diag_*.py and bench.py's stream
-# ceiling, never by the product.  The measured-slower kernels and the measurement entry points live in
-# $(CSRC)/diag/ (*.inc included under -DBF_DIAG, and the diagnostic-only bf_wide_i8os.hip).
-DIAG_LIB := build/libbf_diag.so
-DIAG_SRCS := $(SRCS) $(CSRC)/diag/bf_wide_i8os.hip
-DIAG_OBJS := $(patsubst $(CSRC)/%,build/diag/%.o,$(DIAG_SRCS))
-diag: $(DIAG_LIB)
-build/diag/%.o: $(CSRC)/% $(HDRS)
-	@mkdir -p $(dir $@)
-	$(HIPCC) $(HIPFLAGS) -DBF_DIAG -x hip -c $< -o $@
-$(DIAG_LIB): $(DIAG_OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(DIAG_OBJS) -ldl

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
                                                                        float* __restrict__ y, int NB, int A, int M,
                                                                        int S, int NT, int nslabs, long long nbpc,
                                                                        int xcd) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int slab;
@@ -340,7 +340,7 @@ template <bool Signed, int NTS, int R, int UPT, int Mode = 0, int G = 2>
 __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
     const uint8_t* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int NB, int A, int M, int S,
     int NT, int nslabs, long long nbpc, int xcd, long long nitems) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -546,7 +546,7 @@ template <bool Signed, int Mode, int NW, int Occ = NW / 2>
 __global__ __launch_bounds__(NW * 64, Occ) void beamform_table_os_kernel(const uint8_t* __restrict__ x,
                                                                       const float* __restrict__ w,
                                                                       float* __restrict__ y, int A) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   constexpr int NTL = kOsCols / 16, RG = 16 / NW, M2 = kOsCols, T = kOsRows;
   constexpr int CPT = 16 / NW;            // table columns per thread
@@ -755,8 +755,7 @@ int launch_persist(const uint8_t* x, const float* w, float* y, long long bpc, in
 template <bool Signed, int NTS>
 int dispatch_vec(const uint8_t* x, const float* w, float* y, long long bpc, int NB, int A, int M, int S, int NT,
                  hipStream_t st) {
-  const char* e = diag_env("BF_TABLE_BASIC");  // tests: force the basic kernel
-  if (A % 4 == 0 && !(e && e[0] == '1')) {
+  if (A % 4 == 0) {
     // ring depth: the k-steps of a row, up to 16 (the steps are padded to a multiple of R); long rows only
     if (S >= 16 && coef_lds_bytes((S + 15) / 16 * 16, NTS) <= kMaxLds) {
       // 256-antenna rows in two-workgroup slabs (config 4): the persistent form, the next slab loaded under the
@@ -770,8 +769,7 @@ int dispatch_vec(const uint8_t* x, const float* w, float* y, long long bpc, int 
     if (S >= 8 && coef_lds_bytes((S + 7) / 8 * 8, NTS) <= kMaxLds)
       return launch_ring<Signed, NTS, 8>(x, w, y, bpc, NB, A, M, S, NT, st);
     // 4..7 k-steps (64 antennas: config 3): a 4-deep ring
-    const char* r4 = diag_env("BF_TABLE_RING4");  // measurement: 0 keeps the basic kernel
-    if (S >= 4 && !(r4 && r4[0] == '0') && coef_lds_bytes((S + 3) / 4 * 4, NTS) <= kMaxLds)
+    if (S >= 4 && coef_lds_bytes((S + 3) / 4 * 4, NTS) <= kMaxLds)
       return launch_ring<Signed, NTS, 4>(x, w, y, bpc, NB, A, M, S, NT, st);
   }
   if (A % 4 == 0) return launch_table<Signed, NTS, true>(x, w, y, bpc, NB, A, M, S, NT, st);
@@ -781,11 +779,10 @@ int dispatch_vec(const uint8_t* x, const float* w, float* y, long long bpc, int 
 template <bool Signed>
 int dispatch_table(const uint8_t* x, const float* w, float* y, long long bpc, int NB, int A, int M, int S, int NT,
                    hipStream_t st) {
-  const char* os = diag_env("BF_TABLE_OS");  // measurement: 0 keeps the slab kernels
   // 4 waves per item (256 VGPRs, two workgroups per CU), spill-free in the one-loop form: 791 us at config 4 against
   // 853 for the 8-wave form (128 VGPRs, spills 24-40 B/lane) and 933 for the 8-wave form bounded to 3 waves per
   // SIMD (no spill, one workgroup per CU), profiles/r4_s_table_os_ab.txt
-  if (table_os_fits(NB, A, M, x, w) && !(os && os[0] == '0')) return launch_table_os<Signed, 0, 4>(x, w, y, bpc, A, st);
+  if (table_os_fits(NB, A, M, x, w)) return launch_table_os<Signed, 0, 4>(x, w, y, bpc, A, st);
   // Long rows (>= 16 k-steps: 256+ antennas): the widest slab whose staged fragments leave room for a second
   // workgroup per CU, so one workgroup's table staging overlaps the other's contraction (cfg4: a 128 KiB slab held
   // one workgroup per CU and ran 3.1 ms); the slabs' re-reads of x hit L2 (XCD-grouped slabs).
@@ -820,7 +817,3 @@ extern "C" int bf_beamform(const uint8_t* x, const float* w, float* y, int B, in
   if (sample_signed) return bf::dispatch_table<true>(x, w, y, bpc, NB, A, M, S, NT, st);
   return bf::dispatch_table<false>(x, w, y, bpc, NB, A, M, S, NT, st);
 }
-
-#ifdef BF_DIAG
-#include "diag/beamform_diag.inc"
-#endif

@@ -13,7 +13,6 @@
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "bf_common.hpp"
 #include "bf_phase.hpp"
@@ -95,6 +94,7 @@ __global__ __launch_bounds__(256) void coeff_gen_tile_kernel(const float4* __res
 // kernels above store 8-byte pairs into rows 2M floats apart).  Cache & 2: non-temporal stores (the table is
 // written once and read by the multiply much later).
 constexpr int kCoefBlockLds = 32 * 1024;
+constexpr int kCoefBlockCache = 2;  // the product's policy (both forms stay instantiated, as bf_reorder.hip's)
 __host__ __device__ inline int coef_block_ants(int A, int M) {
   int na = kCoefBlockLds / 16 / (M + 1);
   if (na >= 16) na &= ~15;
@@ -222,22 +222,19 @@ extern "C" int bf_coeff_gen(const float* delay_vals, float* out, int B, int P, i
   BF_REQUIRE((reinterpret_cast<uintptr_t>(delay_vals) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
              "bf_coeff_gen: misaligned buffer");
   BF_REQUIRE(static_cast<long long>(A) * M < (1LL << 31) && C < 65536, "bf_coeff_gen: shape too large");
-  const char* form = bf::diag_env("BF_COEFF_FORM");  // measurement: "thread" / "tile" = the per-(a, m) kernels
   const int na = bf::coef_block_ants(A, M);
   // the block form stores 16-byte pieces (every antenna pair's rows start 16 M bytes apart): it needs a 16-byte
   // aligned table; an 8-byte aligned one (a C-ABI caller's offset pointer) takes the per-(a, m) kernels below
-  if (!form && na >= 1 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+  if (na >= 1 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
     const unsigned gx = static_cast<unsigned>((A + na - 1) / na);
     const size_t lds = static_cast<size_t>(na) * (M + 1) * 16;
-    const char* nt = bf::diag_env("BF_COEFF_NT");
-    const char* bg = bf::diag_env("BF_COEFF_BPG");  // measurement: (b, p) planes per workgroup
     // up to 4 (b, p) planes per workgroup: cfg3 (16 planes) 245 -> 189 us, non-temporal (plain 245 us); one plane
     // per workgroup recomputes the phasors too often (300 us) -- profiles/r3_k_ops_ab.txt
-    const int bpg = bg ? std::max(1, atoi(bg)) : std::min(B * P, 4);
+    const int bpg = std::min(B * P, 4);
     const unsigned gz = static_cast<unsigned>((B * P + bpg - 1) / bpg);
     const auto dv = reinterpret_cast<const float4*>(delay_vals);
     const long long base = static_cast<long long>(C) * xeng_id;
-    if (nt && nt[0] == '0')
+    if (bf::kCoefBlockCache == 0)
       hipLaunchKernelGGL(bf::coeff_gen_block_kernel<0>, dim3(gx, static_cast<unsigned>(C), gz), dim3(256), lds,
                          bf::as_stream(stream), dv, out, B * P, C, A, M, na, bpg, base, static_cast<double>(Ctot),
                          sample_period);
@@ -247,7 +244,7 @@ extern "C" int bf_coeff_gen(const float* delay_vals, float* out, int B, int P, i
                          sample_period);
     BF_LAUNCHED("coeff_gen_block_kernel");
   }
-  if (A >= 32 && M >= 32 && !(form && form[0] == 't' && form[1] == 'h')) {  // many antennas and beams: the tiled, coalesced-read form
+  if (A >= 32 && M >= 32) {  // many antennas and beams: the tiled, coalesced-read form
     const unsigned gx = static_cast<unsigned>(((A + bf::kCoefTile - 1) / bf::kCoefTile) *
                                               ((M + bf::kCoefTile - 1) / bf::kCoefTile));
     hipLaunchKernelGGL(bf::coeff_gen_tile_kernel, dim3(gx, static_cast<unsigned>(C)), dim3(256), 0,

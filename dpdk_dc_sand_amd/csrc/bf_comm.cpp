@@ -101,16 +101,10 @@ int rccl_fail(ncclResult_t e, const char* what) {
 // Bytes per RCCL group of a scatter.  A piece is a block of whole (b, a) rows, or a segment of one row when a row is
 // longer than this: no group moves more.  Why: RCCL 2.27.7's point-to-point drops bytes of large messages -- a
 // single self ncclSend/ncclRecv of more than 1 GiB leaves every byte past 2^30 unwritten, while the 2-D pack of the
-// same slice (hipMemcpy2DAsync) is intact; attributed stage by stage on the device (tools/diag_scatter.py
-// --attribute, profiles/r5_a_scatter_attribution.txt: 1 GiB ok; 2047 and 2048 MiB wrong from byte 2^30 on, pack ok).
+// same slice (hipMemcpy2DAsync) is intact; attributed stage by stage on the device
+// (profiles/r5_a_scatter_attribution.txt: 1 GiB ok; 2047 and 2048 MiB wrong from byte 2^30 on, pack ok).
 // With 256 MiB pieces every size verifies (tests/test_gpu_multi_rank.py: 2 GiB slices, rows over 256 MiB).
 constexpr size_t kScatterChunk = size_t(256) << 20;
-#ifdef BF_DIAG
-size_t g_scatter_chunk = kScatterChunk;  // measurement knob (bf_diag_scatter_chunk): attribute the truncation
-inline size_t scatter_chunk() { return g_scatter_chunk; }
-#else
-constexpr size_t scatter_chunk() { return kScatterChunk; }
-#endif
 
 namespace {
 // One piece of a slice: `nrows` rows from `row0`, bytes [off, off + width) of each.  Either width == run (whole rows,
@@ -310,7 +304,7 @@ int bf_scatter_plan(int nranks, int rank, int root, int B, int A, int C, int T, 
              "bf_scatter_plan: rank %d, root %d of %d ranks", rank, root, nranks);
   BF_REQUIRE(B > 0 && A > 0 && C > 0 && T > 0, "bf_scatter_plan: bad shape B=%d A=%d C=%d T=%d", B, A, C, T);
   const size_t run = static_cast<size_t>(C) * T * 4;
-  const auto plan = scatter_plan(nranks, rank, root, static_cast<size_t>(B) * A, run, chunk ? chunk : scatter_chunk(),
+  const auto plan = scatter_plan(nranks, rank, root, static_cast<size_t>(B) * A, run, chunk ? chunk : kScatterChunk,
                                  staging_bytes);
   *n_ops = plan.size();
   if (ops == nullptr) return BF_OK;
@@ -330,7 +324,7 @@ int bf_channel_scatter(bf_comm* c, const uint8_t* band, uint8_t* slice, int B, i
   hipStream_t st = bf::as_stream(stream);
   size_t need = 0;
   const auto plan = scatter_plan(c->nranks, c->rank, root, static_cast<size_t>(B) * A, static_cast<size_t>(C) * T * 4,
-                                 scatter_chunk(), &need);
+                                 kScatterChunk, &need);
   if (need > c->staging_bytes) {
     if (c->staging) {
       BF_HIP(hipEventSynchronize(c->sent));
@@ -393,35 +387,5 @@ int bf_comm_load(void) {
   bf::clear_error();
   return BF_OK;
 }
-
-#ifdef BF_DIAG
-// ---- diagnostic build: attributing the round-4 2 GiB truncation (tools/diag_scatter.py --attribute) ----
-// The scatter's piece size; 0 restores the product's.
-int bf_diag_scatter_chunk(size_t bytes) {
-  g_scatter_chunk = bytes ? bytes : kScatterChunk;
-  return BF_OK;
-}
-// The pack stage alone: one hipMemcpy2DAsync of `height` rows of `width` bytes (pitches as given).
-int bf_diag_memcpy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height,
-                     void* stream) {
-  BF_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, bf::as_stream(stream)));
-  return BF_OK;
-}
-// The RCCL stage alone: one group of a self ncclSend(src) + ncclRecv(dst) of `bytes` on a one-rank communicator.
-int bf_diag_p2p_self(bf_comm* c, const void* src, void* dst, size_t bytes, void* stream) {
-  BF_REQUIRE(c != nullptr && c->nranks == 1, "bf_diag_p2p_self: needs a one-rank communicator");
-  DeviceGuard dg(c->device);
-  hipStream_t st = bf::as_stream(stream);
-  BF_RCCL(rccl().group_start());
-  ncclResult_t e = rccl().send(src, bytes, ncclUint8, 0, c->comm, st);
-  if (e == ncclSuccess) e = rccl().recv(dst, bytes, ncclUint8, 0, c->comm, st);
-  if (e != ncclSuccess) {
-    (void)rccl().group_end();
-    return rccl_fail(e, "bf_diag_p2p_self");
-  }
-  BF_RCCL(rccl().group_end());
-  return BF_OK;
-}
-#endif  // BF_DIAG
 
 }  // extern "C"

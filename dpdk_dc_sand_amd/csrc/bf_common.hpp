@@ -7,7 +7,6 @@
 
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 
@@ -48,25 +47,8 @@ inline int hip_fail(hipError_t e, const char* what) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Measurement knobs (load forms, slab widths, launch orders) are read from the environment only in the diagnostic
-// build (`make diag`, -DBF_DIAG, used by tools/diag_*.py).  The product library never reads the environment: kernel
-// paths and contract switches are explicit bf_beamform_fused flags (include/bf.h).
-inline const char* diag_env(const char* name) {
-#ifdef BF_DIAG
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
-// The kernels' compile-time `Mode` ablation bits (skip a phase, stamp, re-route a stream) exist for the diagnostic
-// build only: a product instantiation carrying one fails to compile (static_assert(kDiagBuild || ...) per kernel).
-#ifdef BF_DIAG
-constexpr bool kDiagBuild = true;
-#else
-constexpr bool kDiagBuild = false;
-#endif
+// The library never reads the environment: kernel paths and contract switches are explicit bf_beamform_fused flags
+// (include/bf.h).
 
 constexpr int kSamplesPerBlock = 16;  // matrix_multiply.py:76 (128 // 8)
 
@@ -94,17 +76,5 @@ inline bool q14_sum_bound_ok(int A, bool sample_signed, double max_gain) {
 
 // Compute units of the current device (cached per device index; sizes persistent grids only).
 int cu_count();
-
-#ifdef BF_DIAG
-// A second stream on the current device for work a call forks off its caller's stream and joins back (the int8
-// wide path's coefficient generator running beside the contraction), and a pool of events for the hand-offs.
-// Thread-local per device: concurrent callers on other host threads never serialise on one another's helper.
-// Returns nullptr (and sets the error) if the stream or events cannot be created.
-struct AuxStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[17] = {};  // [0] fork, [1 + k] chunk k done
-};
-AuxStream* aux_stream();
-#endif
 
 }  // namespace bf

@@ -310,7 +310,7 @@ __device__ void store_f32acc_i8_rows(const FusedArgs& P, int b, int c, int p, in
 // add are one exact FMA (as requant_bits<true>).
 template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, int Mode = 0, int Occ = 1, bool Pow2 = false>
 __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_item_kernel(FusedArgs P) {
-  static_assert(kDiagBuild || (Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert((Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -883,7 +883,7 @@ __device__ void store_f32acc_i8_rows(const FusedArgs& P, int b, int c, int p, in
 // Pow2: out_scale * 2^-14 is a power of two (requant_bits<true>: one exact FMA).
 template <bool Signed, int NTS, bool Full, int Mode = 0, int Occ = 3, bool A64 = false, bool Pow2 = false>
 __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(FusedArgs P) {
-  static_assert(kDiagBuild || (Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert((Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -1142,8 +1142,7 @@ int launch_i8_item(FusedArgs P, hipStream_t st, size_t min_lds = 0) {
   const size_t lds = std::max<size_t>(static_cast<size_t>(2) * NTS * 2 * 64 * 16 + 4 * 32 * 4, min_lds);
   const long long n_items = static_cast<long long>(P.nslabs) * P.B * P.C;
   BF_REQUIRE(n_items < (1LL << 31), "bf_beamform_fused: too many items");
-  const char* ae = diag_env("BF_I8_A64");  // measurement: 0 forces the clamped per-lane addressing
-  const bool a64 = P.A == 64 && 24ull * P.C * P.T * 4 + P.T * 4ull < (1ull << 32) && !(ae && ae[0] == '0');
+  const bool a64 = P.A == 64 && 24ull * P.C * P.T * 4 + P.T * 4ull < (1ull << 32);
   const bool pow2 = scale_is_pow2(P.out_scale * 0x1p-14f);  // the requantisation's exact single FMA
   const dim3 grid(static_cast<unsigned>(n_items)), block(kThreads);
   if (a64 && pow2)
@@ -1163,7 +1162,7 @@ int launch_i8(FusedArgs P, hipStream_t st) {
   const int choice = fused_kernel_choice(P);
   const bool small = S8 <= 2 && P.T <= 256;
   // the 32-beam slab kernels up to A = 512 (their Q14 limb image in LDS); beyond, the generic kernel (groups of 64
-  // antennas).  (The round-1 16-beam slab kernel, which also covered 512 < A <= 724, is in the diagnostic build only.)
+  // antennas).  (The round-1 16-beam slab kernel, which also covered 512 < A <= 724, was removed with the diagnostic build.)
   if ((choice == BF_FUSED_PATH_WIDE || (choice == 0 && !small)) && i8_w32_fits(P)) return launch_i8_w32<Signed>(P, st);
   if (small && choice != BF_FUSED_PATH_GENERIC) {
     const int M2 = 2 * P.M;
@@ -1255,8 +1254,7 @@ int dispatch(FusedArgs P, hipStream_t st) {
     if (M2 == 16) return launch_item<Signed, OutI8, 1, Exact, true, 0, kOcc>(P, st);
     return launch_item<Signed, OutI8, 1, Exact, false, 0, kOcc>(P, st);
   }
-  const char* wn = diag_env("BF_FUSED_GENERIC_NTS");  // measurement: force the slab width
-  const int want = wn ? atoi(wn) : 2;
+  const int want = 2;  // the generic kernel's widest slab
   if (want >= 4 && P.NT >= 4 && coef_lds_bytes(P.S, 4) <= kMaxLds) return launch_generic<Signed, OutI8, 4, Exact>(P, st);
   if (want >= 2 && P.NT >= 2 && coef_lds_bytes(P.S, 2) <= kMaxLds) return launch_generic<Signed, OutI8, 2, Exact>(P, st);
   return launch_generic<Signed, OutI8, 1, Exact>(P, st);
@@ -1366,7 +1364,3 @@ extern "C" double bf_fused_algorithmic_bytes(int B, int C, int T, int A, int M, 
   const double dly = static_cast<double>(delay_channels) * M * A * 16.0;
   return vin + vout + dly;
 }
-
-#ifdef BF_DIAG
-#include "diag/fused_diag.inc"
-#endif

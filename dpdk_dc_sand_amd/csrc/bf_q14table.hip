@@ -55,7 +55,7 @@ __device__ __forceinline__ bool w32_slot_antenna(int sa, int A, int* a) {
 // 2 the stores without the walk (each word its channel index).
 template <bool Gain, int Mode = 0>
 __global__ __launch_bounds__(256) void q14_table_kernel(Q14TableArgs P) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   const int b = blockIdx.z;
   const int c0 = blockIdx.y * P.run;
   const int w = blockIdx.x * 256 + threadIdx.x;  // word within a (b, c[, slab]) block
@@ -200,10 +200,6 @@ __global__ __launch_bounds__(256) void q14_table_kernel(Q14TableArgs P) {
   }
 }
 
-#ifdef BF_DIAG
-#include "diag/q14_image.inc"  // the halved-image generator (diagnostic build only)
-#endif
-
 }  // namespace
 
 int launch_q14_table(const FusedArgs& P, uint32_t* out, int layout, hipStream_t st) {
@@ -223,42 +219,11 @@ int launch_q14_table(const FusedArgs& P, uint32_t* out, int layout, hipStream_t 
                                                    : 1024LL * Q.Sp * Q.nslabs;
   // measurement: channels per recurrence run (16 / 32 / 64 / 128 / 256: 97 / 88 / 78-80 / 78 / 81 us at config 4;
   // four words per thread with 16-byte stores, plain or non-temporal: 87-90 us -- profiles/r3_o_generator_sweep.txt)
-  const char* rn = diag_env("BF_Q14_RUN");
-  Q.run = rn ? std::max(1, atoi(rn)) : kQ14Run;
-  const char* uf = diag_env("BF_Q14_UNIT");  // measurement: 0 = the two-sided decision for unit gains too
-  Q.unit_fast = !(uf && uf[0] == '0');
-#ifdef BF_DIAG
-  if (layout == kLayoutW32H) {  // one 1024-thread workgroup per (b, run, slab, 16-beam tile)
-    Q.run = std::min(Q.run, kQ14Run);
-    const long long gy = (Q.Cn + Q.run - 1) / Q.run;
-    BF_REQUIRE(Q.Sp <= 8 && gy < 65536 && P.B < 65536 && Q.nslabs < 32768, "q14 image: shape too large");
-    const dim3 grid(static_cast<unsigned>(2 * Q.nslabs), static_cast<unsigned>(gy), P.B);
-    if (P.delay_channels != 1 && P.gain)
-      hipLaunchKernelGGL((q14_image_kernel<true, true>), grid, dim3(1024), 0, st, Q);
-    else if (P.delay_channels != 1)
-      hipLaunchKernelGGL((q14_image_kernel<false, true>), grid, dim3(1024), 0, st, Q);
-    else if (P.gain)
-      hipLaunchKernelGGL((q14_image_kernel<true, false>), grid, dim3(1024), 0, st, Q);
-    else
-      hipLaunchKernelGGL((q14_image_kernel<false, false>), grid, dim3(1024), 0, st, Q);
-    BF_LAUNCHED("q14_image_kernel");
-  }
-#else
-  BF_REQUIRE(layout != kLayoutW32H, "q14 table: the halved-image layout is in the diagnostic build only");
-#endif
+  Q.run = kQ14Run;
+  Q.unit_fast = true;  // (false: the two-sided decision for unit gains too)
+  BF_REQUIRE(layout != kLayoutW32H,
+             "q14 table: the halved-image layout has no generator (removed with the diagnostic build)");
   Q.run = std::min(Q.run, 64);  // (the deferred-fixup mask of q14_table_kernel holds 64 channels)
-#ifdef BF_DIAG
-  const char* gm = diag_env("BF_Q14_MODE");
-  if (gm && (atoi(gm) == 1 || atoi(gm) == 2)) {  // measurement: the walk without stores (1) / stores only (2)
-    const long long gx0 = (words + 255) / 256, gy0 = (Q.Cn + Q.run - 1) / Q.run;
-    const dim3 grid(static_cast<unsigned>(gx0), static_cast<unsigned>(gy0), P.B);
-    if (atoi(gm) == 1)
-      hipLaunchKernelGGL((q14_table_kernel<false, 1>), grid, dim3(256), 0, st, Q);
-    else
-      hipLaunchKernelGGL((q14_table_kernel<false, 2>), grid, dim3(256), 0, st, Q);
-    BF_LAUNCHED("q14_table_kernel");
-  }
-#endif
   const long long gx = (words + 255) / 256, gy = (Q.Cn + Q.run - 1) / Q.run;
   BF_REQUIRE(gx < (1LL << 31) && gy < 65536 && P.B < 65536, "q14 table: grid too large");
   if (P.gain)

@@ -10,7 +10,6 @@
 // per iteration).  For A % 8 == 0 a thread reads the 8 antennas' dwords of one time sample (both pols) and splits
 // them with v_perm into the two pols' outputs; other A use 2-byte transposed reads.  The odd dword pitch (TT + 1)
 // keeps the transposed LDS reads (nearly) bank-conflict-free.
-#include <cstdlib>
 
 #include "bf_common.hpp"
 
@@ -163,20 +162,16 @@ extern "C" int bf_reorder(const uint8_t* in, uint8_t* out, int B, int A, int C, 
   BF_REQUIRE((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
              "bf_reorder: buffers must be 16-byte aligned");
   // Largest power-of-two time chunk (>= 8, dividing T) whose LDS image fits 64 KiB.
-  const char* ttc = bf::diag_env("BF_REORDER_TT");  // measurement: cap the time chunk
-  const int tt_cap = ttc ? atoi(ttc) : 1 << 30;
   int TT = 1;
-  while (TT * 2 <= T && T % (TT * 2) == 0 && TT * 2 <= tt_cap) TT *= 2;
+  while (TT * 2 <= T && T % (TT * 2) == 0) TT *= 2;
   while (TT > 8 && static_cast<long long>(A) * (TT * 4 + 4) > 65536) TT /= 2;
   BF_REQUIRE(static_cast<long long>(A) * (TT * 4 + 4) <= 65536, "bf_reorder: n_ants=%d too large", A);
   const int nchunk = T / TT;
   const long long grid = static_cast<long long>(B) * C * nchunk;
   BF_REQUIRE(grid < (1LL << 31), "bf_reorder: grid too large");
   const size_t lds = static_cast<size_t>(A) * (TT + 1) * 4;
-  const char* e = bf::diag_env("BF_REORDER_ORDER");  // measurement: "channel" keeps the plain order
-  const int xcd_range = grid % 8 == 0 && !(e && e[0] == 'c');
-  const char* nt = bf::diag_env("BF_REORDER_NT");  // measurement: cache policy bits (1 loads, 2 stores)
-  const int cache = nt ? atoi(nt) : kReorderCache;
+  const int xcd_range = grid % 8 == 0;
+  const int cache = kReorderCache;
   if (A % 8 == 0)
     bf::launch_reorder<true>(cache, dim3(static_cast<unsigned>(grid)), lds, bf::as_stream(stream), in, out, A, C, T,
                              TT, nchunk, xcd_range);

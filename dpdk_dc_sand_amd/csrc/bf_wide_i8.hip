@@ -1,6 +1,6 @@
 // Integer wide fused beamformer: many antennas x beams (config 4: 256 antennas, 64 beams), int8 beams, bit-exact.
 // The 32-beam slab kernels are the product (BF_FUSED_PATH_WIDE); the measured-slower forms (the round-1 16-beam slabs,
-// round 4's halved-image kernel) and the measurement entry points live in diag/*.inc, compiled only with -DBF_DIAG.
+// round 4's halved-image kernel, round 6's ring and loader-wave forms) are recorded in DESIGN.md only.
 //
 // Same integer contract as beamform_fused_i8_item_kernel (oracle.fused_beamform_int8: Q14 coefficients of the
 // exact float32 phasors, exact int32 products, one float rounding to int8), organised like the float wide kernel
@@ -24,10 +24,6 @@ constexpr int kW8Threads = 256;
 __device__ __forceinline__ int w8_step_base(int s, int A) { return min(32 * s, A - 32); }
 // k-steps of 32 antennas, padded to an even count (ping-pong, see the float wide kernel)
 __host__ __device__ inline int w8_padded_steps(int A) { return 2 * ((((A + 31) >> 5) + 1) / 2); }
-
-#ifdef BF_DIAG
-#include "diag/wide_i8_w8.inc"  // the 16-beam slab kernel (diagnostic build only)
-#endif
 
 // ---- 32-beam slabs (the default integer wide kernel) -------------------------------------------------------------
 // The 16-beam kernel above re-reads each item's voltages once per slab (4x at 64 beams) with a prefetch distance of
@@ -236,7 +232,7 @@ __device__ __forceinline__ void w32_mfma_pf(const int4* __restrict__ fr, int s, 
 // without the phasor math, 256 the phasor math on register-made delays (no model loads).
 template <bool Signed, int Mode = 0, bool Gain = false>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(FusedArgs P) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) int4 lds4[];
   // Mode 128 (diagnostics): per-wave s_memtime cycles of the phases -> P.gain as uint64 [wave][4]: coefficient
   // phase (to the barrier), contraction loops, requantise + stores, total
@@ -542,7 +538,7 @@ constexpr int kW32TChannels = 4;
 template <bool Signed, int Mode = 0, bool Early = true, int kSp = 0, int kNP = 0, int kNB = 4, int kCh = kW32TChannels,
           bool BufLd = false, bool Pow2 = false>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(FusedArgs P) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) int4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -876,7 +872,7 @@ __device__ __forceinline__ i32x4_t w32r_frag_im(const i32x4_t& f) {
 // slab's voltage DMA through a zero-record descriptor (one slab's bytes through the CU path: wrong beams for it).
 template <bool Pow2, int Mode = 0>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(FusedArgs P) {
-  static_assert(kDiagBuild || Mode == 0, "diagnostic Mode bits in a product instantiation");
+  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   constexpr int Sp = 8, NP = 2, kCh = kW32RChannels;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1151,18 +1147,8 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-#ifdef BF_DIAG
-#include "diag/wide_i8_w32h.inc"  // round 4's halved-image kernel (diagnostic build only)
-#include "diag/wide_i8_w32r3.inc"  // round 6's three-slot ring (measured slower; diagnostic build only)
-#include "diag/wide_i8_w32s.inc"  // round 6's loader-wave form (measured slower; diagnostic build only)
-#endif
-
 template <bool Signed, int Mode>
 int launch_w32t_contract(FusedArgs P, hipStream_t st);
-#ifdef BF_DIAG
-template <bool Signed, int Mode>
-int launch_w32_overlapped(FusedArgs P, int k, hipStream_t st);
-#endif
 
 // The LDS-DMA ring contraction's shape (beamform_fused_i8_w32r_kernel): 8 k-steps, T = 256, whole 32-beam slabs,
 // every in-workgroup voltage offset and every beam offset below 2^31, a whole launch (no channel chunk).
@@ -1198,39 +1184,6 @@ int launch_w32(FusedArgs P, hipStream_t st) {
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
   if (P.table && w32_table_fits(P.A) && P.table_bytes >= w32_table_bytes(P.B, P.C, P.A, P.M)) {
     // the coefficient table of this launch, written by q14_table_kernel just before on `st`
-#ifdef BF_DIAG
-    // measurement (BF_W32_CHUNKS): generator and contraction alternated over channel chunks
-    const char* ck = diag_env("BF_W32_CHUNKS");
-    const int nchunks = ck ? std::max(1, atoi(ck)) : 1;
-    if (nchunks > 1 && P.B == 1 && P.c_count == 0 && P.delay_channels == 1) {
-      const int per = (P.C + nchunks - 1) / nchunks;
-      for (int c0 = 0; c0 < P.C; c0 += per) {
-        FusedArgs Q = P;
-        Q.c_count = std::min(per, P.C - c0);
-        Q.raw = P.raw + static_cast<size_t>(c0) * P.T * 4;
-        Q.y = static_cast<int8_t*>(P.y) + static_cast<size_t>(c0) * P.T * 2 * P.M;
-        Q.table = P.table + static_cast<size_t>(c0) * ((P.M + 31) / 32) * 1024 * w32_table_steps(P.A);
-        Q.base_ch = P.base_ch + c0;
-        const int e = launch_w32<Signed, Mode>(Q, st);
-        if (e != BF_OK) return e;
-      }
-      return BF_OK;
-    }
-    // measurement (BF_W32_OVERLAP = k chunks): the generator's chunks on a second stream, each chunk's contraction
-    // on the caller's stream after its chunk of the table.  Measured slower than the serial pair (round 4,
-    // profiles/r4_s_overlap_ab.txt: 2 / 4 / 8 chunks 494 / 505 / 843 vs 478 us, bitwise equal), so diagnostic only.
-    const char* ov = diag_env("BF_W32_OVERLAP");
-    const int nover = ov ? std::min(16, std::max(1, atoi(ov))) : 1;
-    if (nover > 1 && P.B == 1 && P.c_count == 0 && P.delay_channels == 1)
-      return launch_w32_overlapped<Signed, Mode>(P, nover, st);
-    // measurement (BF_W32H=1): the halved-image generator + the w32h contraction at config 4's shape -- bitwise equal
-    // to the table kernel, measured no faster (profiles/r4_*)
-    if (Mode == 0 && w32h_fits(P) && diag_env("BF_W32H")) {
-      const int e = launch_q14_table(P, const_cast<uint32_t*>(P.table), kLayoutW32H, st);
-      if (e != BF_OK) return e;
-      return launch_w32h_contract<Signed>(P, st);
-    }
-#endif
     const int e = launch_q14_table(P, const_cast<uint32_t*>(P.table), kLayoutW32, st);
     if (e != BF_OK) return e;
     if constexpr (Signed && Mode == 0)
@@ -1281,10 +1234,6 @@ int launch_w32t_contract(FusedArgs P, hipStream_t st) {
   }
 }
 
-#ifdef BF_DIAG
-#include "diag/wide_i8_overlap.inc"  // generator / contraction overlap (measured slower)
-#endif
-
 }  // namespace
 
 bool i8_w32_fits(const FusedArgs& P) {
@@ -1302,7 +1251,3 @@ template int launch_i8_w32<false>(FusedArgs, hipStream_t);
 template int launch_i8_w32<true>(FusedArgs, hipStream_t);
 
 }  // namespace bf
-
-#ifdef BF_DIAG
-#include "diag/wide_i8_entries.inc"
-#endif

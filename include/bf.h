@@ -158,7 +158,7 @@ int bf_beamform(const uint8_t* x, const float* w, float* y, int B, int P, int C,
 #define BF_FUSED_PATH_WIDE 0x0400    /* many antennas x beams: multi-wave beam slabs (config 4) */
 /* (0x0200 and 0x0600 named two measured-slower kernels of ABI 1.x, and 0x0500 (WIDE16) the 16-beam int8 wide kernel
  * of ABI 2.0, removed from the product in ABI 3.0 (0x0500: the 16-beam float slabs are what WIDE picks for M <= 16; the
- * int8 kernel lives on in the diagnostic build): all three are rejected as unknown.) */
+ * int8 kernel is gone with the diagnostic build): all three are rejected as unknown.) */
 #define BF_FUSED_ORDER_MASK 0x3000
 #define BF_FUSED_ORDER_CHANNEL 0x1000 /* plain channel-fastest workgroup order (the persistent config-4 float
                                          kernel walks channel runs and has none: this flag takes the slab kernel) */

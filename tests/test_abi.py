@@ -143,7 +143,7 @@ def test_template_int8_overflow_bound():
 
 def test_product_library_never_reads_the_environment():
     """Kernel choice and contract switches are explicit flags: the product libbf.so imports no getenv (the
-    measurement knobs live in the BF_DIAG build only)."""
+    measurement knobs of the former diagnostic build are gone from the sources)."""
     import shutil
     import subprocess
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"

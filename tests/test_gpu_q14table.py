@@ -200,7 +200,7 @@ def test_int8_table_path_channel_groups(context, command_queue, A, C, B, weighte
     workgroup, C % 4 = 1, 2; 8 at A = 256, C % 8 = 4), two batches, 1, 2, 4 and 8 k-steps (A = 32 ... 256), more
     workgroups than CUs.  Bitwise equal to
     the in-kernel-phasor slab kernel (itself pinned to the oracle above and in test_gpu_fullsize.py).  (These shapes
-    also pinned the output-stationary LDS-DMA kernel measured in round 3, bf_wide_i8os.hip, diagnostic build.)"""
+    also pinned the output-stationary LDS-DMA kernel measured in round 3, since removed with the diagnostic build.)"""
     M, T = 64, 256
     d = delays(1, M, A, seed=A + C)
     rng = np.random.default_rng(A * 3 + C)

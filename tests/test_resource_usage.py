@@ -1,7 +1,6 @@
 """Build hygiene of the product kernels (no GPU): every kernel instance libbf.so contains compiles for gfx950 with no
 scratch (register spills) and without failed unroll requests.  Runs hipcc on the product sources (device code only,
-the Makefile's flags) with -Rpass-analysis=kernel-resource-usage, as tools/resource_usage.py does; the diagnostic
-build (BF_DIAG) is not checked."""
+the Makefile's flags) with -Rpass-analysis=kernel-resource-usage, as tools/resource_usage.py does."""
 import os
 import re
 import shutil

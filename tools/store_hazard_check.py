@@ -1,7 +1,7 @@
 """The store-data hazard of wide vector stores on gfx950: a VALU write to a VGPR that a just-issued dwordx3/x4 store
 still reads as data corrupts what that store writes for the last lanes it reads.  hipcc (ROCm 7.2) does not always
 keep the two apart: round 5 found a `buffer_store_dwordx4 v[80:83]` followed at once by a write of v83, and the 4th
-dword of lanes 12-15 of every row went out wrong in ~1e-5 of the bytes, varying run to run (tools/diag_w32r.py) --
+dword of lanes 12-15 of every row went out wrong in ~1e-5 of the bytes, varying run to run --
 also the signature of round 4's unexplained w64h race.  This scans a source's device ISA for a VALU (or permlane
 swap) writing a wide store's data VGPRs within `window` instructions of it.
 Also: inline-asm results that reach an MFMA operand unpadded (scan_asm_to_mfma).

@@ -1,7 +1,7 @@
 // The box's HBM stream ceiling as a small stand-alone library (build/libbf_stream.so, `make stream`): bench.py's
-// `ceiling` blocks time the fused kernels' read/write byte mix through these plain streams, so the bench no longer
-// needs the whole diagnostic build (build/libbf_diag.so) on the GPU box.  Measurement only, never the product.
-#include "../dpdk_dc_sand_amd/csrc/diag/stream_kernels.hpp"
+// `ceiling` blocks time the fused kernels' read/write byte mix through these plain streams.  Measurement only, never the
+// product.
+#include "stream_kernels.hpp"
 
 // code: 1 plain 16-byte loads/stores, 101 non-temporal stores, 102 non-temporal loads, 103 both (grid-stride over
 // max(in, out) pieces); 200 / 201 the 4:1 read:write mix (out_bytes = in_bytes / 4) with / without non-temporal

@@ -1,6 +1,6 @@
 // The HBM stream-ceiling kernels: plain streams over a read/write byte mix, the achievable ceiling a fused kernel's
-// traffic is compared with.  Included by the diagnostic build (fused_diag.inc) and by the small measurement library
-// bench.py loads for its `ceiling` blocks (tools/stream_ceiling.hip -> build/libbf_stream.so).  Not product code.
+// traffic is compared with.  Included by the small measurement library bench.py loads for its `ceiling` blocks
+// (tools/stream_ceiling.hip -> build/libbf_stream.so).  Not product code.
 #pragma once
 #include <hip/hip_runtime.h>
 
