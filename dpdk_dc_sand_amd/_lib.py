@@ -22,6 +22,7 @@ P_size_t, P_longlong = ctypes.POINTER(c_size_t), ctypes.POINTER(c_longlong)
 PROTOTYPES = {
     "bf_last_error": (c_char_p, []),
     "bf_abi_version": (c_int, []),
+    "bf_has_feature": (c_int, [c_char_p]),
     "bf_device_count": (c_int, [P_int]),
     "bf_set_device": (c_int, [c_int]),
     "bf_get_device": (c_int, [P_int]),
@@ -80,6 +81,9 @@ PROTOTYPES = {
     "bf_pipeline_stage_ms": (c_int, [c_void_p, c_longlong, P_float, P_float, P_float]),
     "bf_requant": (c_int, [c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
     "bf_fused_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_incoherent_beam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                   c_void_p]),
+    "bf_incoherent_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -99,6 +103,8 @@ FUSED_SIGNED, FUSED_OUT_INT8, FUSED_EXACT_COEFF, FUSED_INT8_VIA_F32 = 1, 2, 4, 8
 # kernel-path / workgroup-order overrides (tests and measurement; every path computes the same contract)
 FUSED_PATH = {"auto": 0, "item": 0x100, "generic": 0x300, "wide": 0x400}
 FUSED_ORDER = {"auto": 0, "channel": 0x1000, "xcd": 0x2000}
+# bf_incoherent_beam flags
+INCOH_SIGNED, INCOH_SUM_POLS = 1, 2
 
 
 class BeamformerError(RuntimeError):

@@ -35,8 +35,12 @@ const char* bf_last_error(void);
 /* ABI version: major * 100 + minor.  300: ABI 3.0 -- 0x0500 (BF_FUSED_PATH_WIDE16, accepted by 2.0) is rejected as an
  * unknown path, and bf_coeff_gen_time_study, bf_comm_stats, bf_comm_load and bf_checksum were added.  301: ABI 3.1 --
  * bf_scatter_plan added (the channel scatter's operation list as a pure host function).  302: ABI 3.2 --
- * bf_beamform_study_single_channel added (the C++ study's fused kernel in its own semantics). */
+ * bf_beamform_study_single_channel added (the C++ study's fused kernel in its own semantics).  Later 3.2 libraries add
+ * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
+ * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes. */
 int bf_abi_version(void);
+/* 1 when this library has the named feature ("incoherent_beam"), 0 for any other name (and for NULL). */
+int bf_has_feature(const char* name);
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
  * The reference gets these from katsdpsigproc.accel / PyCUDA (accel.create_some_context,
@@ -203,6 +207,24 @@ int bf_q14_coeffs(const float* delay_vals, int delay_channels, const float* gain
 
 /* 8-bit requantiser (no reference counterpart; SURVEY §7 build step 7): q = clamp(rne(y*scale), -127, 127). */
 int bf_requant(const float* y, int8_t* q, size_t n, float scale, void* stream);
+
+/* Incoherent beam (no reference counterpart): the power re^2 + im^2 of every antenna, summed over a set of antennas
+ * and integrated over windows of `tint` samples, per pol and channel, from the fused operator's own input cube:
+ *   raw      : 8-bit (B, A, C, T, 2, 2), uint8, or int8 with BF_INCOH_SIGNED (the sample_signed convention)
+ *   ant_mask : u8 (A,) on the device, antenna a counts when ant_mask[a] != 0; NULL = every antenna
+ *   out      : f32 (B, 2, C, T/tint), or (B, 1, C, T/tint) with BF_INCOH_SUM_POLS (the two pols added before scaling)
+ *   S[b][p][c][j] = sum over counted a, t in [j*tint, (j+1)*tint) of re^2 + im^2          (exact integer)
+ *   out           = float32(float64(S) * float64(scale))      (one float64 multiply, one round-to-nearest-even)
+ * S does not depend on the order of summation and every output element is written once (no atomics: `out` need not
+ * be zeroed), so the result is deterministic and bit-exact.  T % 16 == 0, T <= 2^20; tint divides T and is a power of
+ * two <= 16 or a multiple of 16; 1 <= A <= 32768 (so S < 2^53); scale finite and > 0; raw 16-byte, out 4-byte
+ * aligned.  A standalone pass over the voltages (bf_incoherent_algorithmic_bytes: 4*B*A*C*T voltage bytes, A mask
+ * bytes when masked != 0, 4*B*(2 or 1)*C*T/tint output bytes). */
+#define BF_INCOH_SIGNED 1
+#define BF_INCOH_SUM_POLS 2
+int bf_incoherent_beam(const uint8_t* raw, const uint8_t* ant_mask, float* out, int B, int C, int T, int A, int tint,
+                       int flags, float scale, void* stream);
+double bf_incoherent_algorithmic_bytes(int B, int C, int T, int A, int tint, int flags, int masked);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

@@ -3,8 +3,12 @@ OpSequence) next to the fused operator, at the SURVEY §8d configurations.  HIP-
 stream, random inputs, algorithmic bytes per launch and the achieved fraction of 8 TB/s.
 
     python tools/bench_ops.py [--reps 10] [--only cfg3,cfg4]     -> one JSON line per measurement
+At cfg2, cfg3 and cfg4 the incoherent beam follows (integration = T and 16, unmasked), each line with the box's stream
+ceiling for the same read and write bytes (build/libbf_stream.so, `make stream`) measured in the same process;
+`--incoherent` runs only these.
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -17,7 +21,8 @@ import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (CoeffGeneratorTemplate, FusedBeamformerTemplate,  # noqa: E402
-                                          MatrixMultiplyTemplate, OpSequenceTemplate, PreBeamformReorderTemplate)
+                                          IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
+                                          PreBeamformReorderTemplate)
 
 TS = 1 / 1712e6
 HBM = 8.0e12
@@ -27,6 +32,7 @@ CONFIGS = {
     "cfg3": dict(A=64, M=16, C=4096, Ctot=4096, T=256, B=8),
     "cfg4": dict(A=256, M=64, C=4096, Ctot=32768, T=256, B=1),
 }
+INCOHERENT_CONFIGS = ("cfg2", "cfg3", "cfg4")
 
 
 def timeit(queue, fn, reps, settle_s=0.2):
@@ -100,18 +106,73 @@ def run_fused(ctx, q, name, c, reps, rng, raw, samples, tag):
         del op
 
 
+def stream_ceiling(ctx, q, in_bytes, out_bytes, reps):
+    """The box's best plain stream over `in_bytes` read and `out_bytes` written (bf_stream_ceiling of
+    build/libbf_stream.so; the grids and codes bench.py tries), timed like the operators.  Every call's return value
+    (the launch's hipError_t) is checked."""
+    path = os.path.join(ROOT, "build", "libbf_stream.so")
+    if not os.path.exists(path):
+        raise OSError(f"{path} not found: build it with `make stream`")
+    lib = ctypes.CDLL(path)
+    V, S, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+    lib.bf_stream_ceiling.restype, lib.bf_stream_ceiling.argtypes = I, [V, V, S, S, I, I, V]
+    src = accel.DeviceArray(ctx, (in_bytes,), np.uint8)
+    dst = accel.DeviceArray(ctx, (max(out_bytes, 16),), np.uint8)
+    src.zero(q)
+    best = None
+    for grid in (1024, 2048):
+        for code in (1, 101, 102, 103) + ((200, 201) if out_bytes * 4 == in_bytes else ()):
+            def fn():
+                st = lib.bf_stream_ceiling(src.ptr, dst.ptr, in_bytes, out_bytes, grid, code, q.handle)
+                if st != 0:
+                    raise RuntimeError(f"bf_stream_ceiling grid {grid} code {code} failed: hipError_t {st}")
+            t = timeit(q, fn, reps, settle_s=0.05)
+            if best is None or t < best[0]:
+                best = (t, grid, code)
+    return best
+
+
+def run_incoherent(ctx, q, name, c, reps, rng):
+    """The incoherent beam over the configuration's voltage cube, unmasked, per pol: integration = T (one window per
+    channel) and 16, each with the stream ceiling for its own read and write bytes."""
+    A, C, T, B = c["A"], c["C"], c["T"], c["B"]
+    raw = accel.DeviceArray(ctx, (B, A, C, T, 2, 2), np.uint8)
+    raw.set(q, rng.integers(0, 256, raw.shape, dtype=np.uint8))
+    for tint in (T, 16):
+        tmpl = IncoherentBeamTemplate(ctx, B, C, T, A, integration=tint)
+        op = tmpl.instantiate(q)
+        op.bind(inSamples=raw)
+        op.ensure_all_bound()
+        t = timeit(q, op, reps)
+        read_bytes, write_bytes = raw.nbytes, op.buffer("outData").nbytes
+        assert tmpl.algorithmic_bytes() == read_bytes + write_bytes
+        ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+        emit(name, f"incoherent_tint{tint}", t, tmpl.algorithmic_bytes(), integration=tint, read_bytes=read_bytes,
+             write_bytes=write_bytes, ceiling_us=round(ct * 1e6, 2),
+             ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+             ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4))
+        del op
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--only", default=",".join(CONFIGS))
     p.add_argument("--fused-only", action="store_true")
+    p.add_argument("--incoherent", action="store_true", help="only the incoherent beam and its stream ceiling")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
     for name in args.only.split(","):
+        if args.incoherent:
+            if name in INCOHERENT_CONFIGS:
+                run_incoherent(ctx, q, name, CONFIGS[name], args.reps, rng)
+            continue
         run_config(ctx, q, name, CONFIGS[name], args.reps, rng, args.fused_only, args.tag)
+        if name in INCOHERENT_CONFIGS and not args.fused_only:
+            run_incoherent(ctx, q, name, CONFIGS[name], args.reps, rng)
 
 
 if __name__ == "__main__":
