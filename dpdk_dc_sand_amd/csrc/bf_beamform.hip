@@ -176,13 +176,12 @@ __global__ __launch_bounds__(kThreads) void beamform_table_kernel(const uint8_t*
 // permlane32_swap -> step 2 s2 = [A0 B0 A1 B1] (k = 8 h + j) and step 2 s2 + 1 = [A2 B2 A3 B3].  Half the load
 // instructions (each still touches 16 row segments), the same per-step fragments and MFMA order (bitwise the same
 // sums as the 8-byte form, and as the fused kernels).
-template <bool Signed, int NTS, int R, int Mode = 0, bool W16 = false>
+template <bool Signed, int NTS, int R, bool W16 = false>
 __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uint8_t* __restrict__ x,
                                                                        const float* __restrict__ w,
                                                                        float* __restrict__ y, int NB, int A, int M,
                                                                        int S, int NT, int nslabs, long long nbpc,
                                                                        int xcd) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int slab;
@@ -209,12 +208,9 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
   // re-deals its loads into exactly the one-step fragments)
   const int kh = 8 * h;
   auto ld = [&](const uint8_t* row, int s) -> uint2 {
-    if constexpr (Mode & 8) return uint2{static_cast<uint32_t>(s + tl), static_cast<uint32_t>(s)};
     return *reinterpret_cast<const uint2*>(row + min(32 * s + kh, K2 - 8));
   };
   auto ld16 = [&](const uint8_t* row, int s2) -> uint4 {  // W16: steps 2 s2, 2 s2 + 1
-    if constexpr (Mode & 8)
-      return uint4{static_cast<uint32_t>(s2 + tl), static_cast<uint32_t>(s2), static_cast<uint32_t>(s2 - tl), 7u};
     return *reinterpret_cast<const uint4*>(row + min(64 * s2 + 2 * kh, K2 - 16));
   };
   const uint8_t* cur_rows[G];
@@ -241,10 +237,8 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
       for (int g = 0; g < G; ++g) ring[r][g] = ld(cur_rows[g], r);
   }
   __builtin_amdgcn_sched_barrier(0);
-  // Mode (diagnostics only): 1 no table staging, 2 no MFMA, 4 no stores, 8 no voltage loads
-  if constexpr (!(Mode & 1))
-    stage_table<NTS>(reinterpret_cast<_Float16*>(lds), w + bpc * static_cast<size_t>(K2) * M2, K2, M2, Sp, tau0, nts,
-                     tid);  // padded steps zero
+  stage_table<NTS>(reinterpret_cast<_Float16*>(lds), w + bpc * static_cast<size_t>(K2) * M2, K2, M2, Sp, tau0, nts,
+                   tid);  // padded steps zero
   __syncthreads();
   if (nrg <= 0) return;
 
@@ -266,12 +260,8 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
             const half8 chi = lds[slot + lane], clo = lds[slot + 64 + lane];
 #pragma unroll
             for (int g = 0; g < G; ++g) {
-              if constexpr (Mode & 2) {
-                acc[g][tau] += __builtin_bit_cast(f32x4, v[g]) + __builtin_bit_cast(f32x4, chi);
-              } else {
-                acc[g][tau] = mfma(chi, v[g], acc[g][tau]);
-                acc[g][tau] = mfma(clo, v[g], acc[g][tau]);
-              }
+              acc[g][tau] = mfma(chi, v[g], acc[g][tau]);
+              acc[g][tau] = mfma(clo, v[g], acc[g][tau]);
             }
           }
         }
@@ -314,13 +304,8 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
       if (j >= nrg) break;
       float* orow = yp + static_cast<size_t>((wave + kWaves * j) * kSamplesPerBlock + tl) * M2;
 #pragma unroll
-      for (int tau = 0; tau < NTS; ++tau) {
-        if constexpr (Mode & 4) {
-          if (acc[g][tau][0] == 1234.5f) orow[tau] = acc[g][tau][1];
-        } else {
-          if (tau < nts) store_f32<NTS>(orow, 16 * (tau0 + tau) + 4 * h, M2, acc[g][tau]);
-        }
-      }
+      for (int tau = 0; tau < NTS; ++tau)
+        if (tau < nts) store_f32<NTS>(orow, 16 * (tau0 + tau) + 4 * h, M2, acc[g][tau]);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -336,11 +321,10 @@ __global__ __launch_bounds__(kThreads) void beamform_table_ring_kernel(const uin
 // between the workgroup's start and its first MFMA.  The ring's last turn of an item prefetches the next item's
 // first steps.  Per item: convert the registers into the LDS slab, barrier, request the next slab, contract, barrier.
 // The MFMA sequence per output is the ring kernel's (bitwise the same results).
-template <bool Signed, int NTS, int R, int UPT, int Mode = 0, int G = 2>
+template <bool Signed, int NTS, int R, int UPT, int G = 2>
 __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
     const uint8_t* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int NB, int A, int M, int S,
     int NT, int nslabs, long long nbpc, int xcd, long long nitems) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -370,13 +354,6 @@ __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
   };
   float tv[UPT][8];
   auto table_load = [&](int slab, size_t bpc) {
-    if constexpr (Mode & 16) {  // diagnostics: no table loads
-#pragma unroll
-      for (int u = 0; u < UPT; ++u)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tv[u][j] = 1e-3f * static_cast<float>(j + u + slab);
-      return;
-    }
     const float* wp = w + bpc * static_cast<size_t>(K2) * M2;
     const int tau0 = slab * NTS;
     // rows past 2A only occur as whole 8-row units (A % 8 == 0): clamp the unit's first row, zeroed at the store
@@ -417,8 +394,6 @@ __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
   };
   const int kh2 = 16 * h;
   auto ld16 = [&](const uint8_t* row, int s2) -> uint4 {
-    if constexpr (Mode & 8)
-      return uint4{static_cast<uint32_t>(s2 + tl), static_cast<uint32_t>(s2), static_cast<uint32_t>(s2 - tl), 7u};
     return *reinterpret_cast<const uint4*>(row + min(64 * s2 + kh2, K2 - 16));
   };
 
@@ -447,7 +422,7 @@ __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
 
   while (true) {
     __syncthreads();  // every wave is done reading the previous slab
-    if constexpr (!(Mode & 1)) table_store(slab);
+    table_store(slab);
     __syncthreads();
     if (itn >= 0) table_load(slab_n, bpc_n);  // in flight during this item's contraction
     const int tau0 = slab * NTS, nts = min(NTS, NT - tau0);
@@ -500,13 +475,8 @@ __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
         if (j >= nrg) break;
         float* orow = yp + static_cast<size_t>((wave + kWaves * j) * kSamplesPerBlock + tl) * M2;
 #pragma unroll
-        for (int tau = 0; tau < NTS; ++tau) {
-          if constexpr (Mode & 4) {
-            if (acc[g][tau][0] == 1234.5f) orow[tau] = acc[g][tau][1];
-          } else {
-            if (tau < nts) store_f32<NTS>(orow, 16 * (tau0 + tau) + 4 * h, M2, acc[g][tau]);
-          }
-        }
+        for (int tau = 0; tau < NTS; ++tau)
+          if (tau < nts) store_f32<NTS>(orow, 16 * (tau0 + tau) + 4 * h, M2, acc[g][tau]);
       }
       // rows of pair pi + 2: this item's, or (past its last pair) the next item's first pairs
 #pragma unroll
@@ -537,16 +507,14 @@ __global__ __launch_bounds__(kThreads, 2) void beamform_table_persist_kernel(
 // the 32-column slab kernels this reads every item's voltages once instead of once per slab (4x at config 4) and the
 // table in whole rows instead of 128-byte row pieces.  Per output the MFMA sequence is the slab kernels' (k-steps in
 // order, hi then lo): bitwise the same sums.  NW = 8: 2 row groups per wave, 128 VGPRs, two workgroups (16 waves)
-// per CU; NW = 4: 4 row groups, 256 VGPRs, two workgroups (8 waves).  Mode (diagnostics): 4 no stores, 8 no voltage
-// loads, 16 no table loads.
+// per CU; NW = 4: 4 row groups, 256 VGPRs, two workgroups (8 waves).
 constexpr int kOsCols = 128, kOsRows = 256;
 constexpr size_t kOsLds = 2 * 2 * 8 * 2 * 64 * 16;  // 2 buffers x 2 steps x 8 tiles x 2 limbs x 64 lanes x 16 B
 
-template <bool Signed, int Mode, int NW, int Occ = NW / 2>
+template <bool Signed, int NW, int Occ = NW / 2>
 __global__ __launch_bounds__(NW * 64, Occ) void beamform_table_os_kernel(const uint8_t* __restrict__ x,
                                                                       const float* __restrict__ w,
                                                                       float* __restrict__ y, int A) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   constexpr int NTL = kOsCols / 16, RG = 16 / NW, M2 = kOsCols, T = kOsRows;
   constexpr int CPT = 16 / NW;            // table columns per thread
@@ -564,13 +532,6 @@ __global__ __launch_bounds__(NW * 64, Occ) void beamform_table_os_kernel(const u
   const int ro = tid / UPR, cq = tid % UPR;  // rows 8 ro .. 8 ro + 7 of a chunk x columns CPT cq ..
   fvec tv[8];
   auto tload = [&](int kc) __attribute__((always_inline)) {
-    if constexpr (Mode & 16) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int i = 0; i < CPT; ++i) tv[j][i] = 1e-3f * (j + i) + 3e-3f * kc;
-      return;
-    }
     // a uniform base + one 32-bit lane offset (the item's table is 2A x 128 floats)
     const uint32_t off = static_cast<uint32_t>(((kc * 64 + 8 * ro) * M2 + CPT * cq) * 4);
 #pragma unroll
@@ -599,12 +560,8 @@ __global__ __launch_bounds__(NW * 64, Occ) void beamform_table_os_kernel(const u
   const uint32_t xoff = static_cast<uint32_t>((RG * wave * 16 + tl) * K2 + 16 * h);  // lane offset in the item
   auto xload = [&](int kc, uint4 (&xr)[RG]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int rg = 0; rg < RG; ++rg) {
-      if constexpr (Mode & 8)
-        xr[rg] = uint4{static_cast<uint32_t>(kc + tl), static_cast<uint32_t>(rg), static_cast<uint32_t>(kc - tl), 7u};
-      else
-        xr[rg] = *reinterpret_cast<const uint4*>(xp + (xoff + static_cast<uint32_t>(rg * 16 * K2 + 64 * kc)));
-    }
+    for (int rg = 0; rg < RG; ++rg)
+      xr[rg] = *reinterpret_cast<const uint4*>(xp + (xoff + static_cast<uint32_t>(rg * 16 * K2 + 64 * kc)));
   };
   f32x4 acc[RG][NTL];
 #pragma unroll
@@ -672,13 +629,7 @@ __global__ __launch_bounds__(NW * 64, Occ) void beamform_table_os_kernel(const u
   for (int rg = 0; rg < RG; ++rg) {
     float* orow = yp + static_cast<size_t>((RG * wave + rg) * 16 + tl) * M2 + 4 * h;
 #pragma unroll
-    for (int t = 0; t < NTL; ++t) {
-      if constexpr (Mode & 4) {
-        if (acc[rg][t][0] == 1234.5f) orow[t] = acc[rg][t][1];
-      } else {
-        *reinterpret_cast<f32x4*>(orow + 16 * t) = acc[rg][t];
-      }
-    }
+    for (int t = 0; t < NTL; ++t) *reinterpret_cast<f32x4*>(orow + 16 * t) = acc[rg][t];
   }
 }
 
@@ -688,10 +639,10 @@ inline bool table_os_fits(int NB, int A, int M, const uint8_t* x, const float* w
          (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
 }
 
-template <bool Signed, int Mode = 0, int NW = 8, int Occ = NW / 2>
+template <bool Signed, int NW = 8, int Occ = NW / 2>
 int launch_table_os(const uint8_t* x, const float* w, float* y, long long bpc, int A, hipStream_t st) {
   BF_REQUIRE(bpc < (1LL << 31), "bf_beamform: grid too large");
-  hipLaunchKernelGGL((beamform_table_os_kernel<Signed, Mode, NW, Occ>), dim3(static_cast<unsigned>(bpc)), dim3(NW * 64),
+  hipLaunchKernelGGL((beamform_table_os_kernel<Signed, NW, Occ>), dim3(static_cast<unsigned>(bpc)), dim3(NW * 64),
                      kOsLds, st, x, w, y, A);
   BF_LAUNCHED("beamform_table_os_kernel");
 }
@@ -710,7 +661,7 @@ int launch_table(const uint8_t* x, const float* w, float* y, long long bpc, int 
   BF_LAUNCHED("beamform_table_kernel");
 }
 
-template <bool Signed, int NTS, int R, int Mode = 0, int Form = 0>
+template <bool Signed, int NTS, int R>
 int launch_ring(const uint8_t* x, const float* w, float* y, long long bpc, int NB, int A, int M, int S, int NT,
                 hipStream_t st) {
   const int nslabs = (NT + NTS - 1) / NTS;
@@ -720,19 +671,19 @@ int launch_ring(const uint8_t* x, const float* w, float* y, long long bpc, int N
   const int xcd = nslabs > 1;
   const long long grid = xcd ? (bpc + 7) / 8 * 8 * nslabs : bpc * nslabs;
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform: grid too large");
-  // Form 0: 16-byte loads when the rows allow them (A % 8 == 0, x 16-byte aligned); 1 (diagnostics): 8-byte loads
-  const bool w16 = Form == 0 && A % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  // 16-byte loads when the rows allow them (A % 8 == 0, x 16-byte aligned)
+  const bool w16 = A % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (w16)
-    hipLaunchKernelGGL((beamform_table_ring_kernel<Signed, NTS, R, Mode, true>), dim3(static_cast<unsigned>(grid)),
+    hipLaunchKernelGGL((beamform_table_ring_kernel<Signed, NTS, R, true>), dim3(static_cast<unsigned>(grid)),
                        dim3(kThreads), lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd);
   else
-    hipLaunchKernelGGL((beamform_table_ring_kernel<Signed, NTS, R, Mode>), dim3(static_cast<unsigned>(grid)),
+    hipLaunchKernelGGL((beamform_table_ring_kernel<Signed, NTS, R>), dim3(static_cast<unsigned>(grid)),
                        dim3(kThreads), lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd);
   BF_LAUNCHED("beamform_table_ring_kernel");
 }
 
 // The persistent ring kernel: UPT table units per thread (Sp * NTS / 4 == UPT), two workgroups per CU.
-template <bool Signed, int NTS, int R, int UPT, int Mode = 0, int G = 2>
+template <bool Signed, int NTS, int R, int UPT, int G = 2>
 int launch_persist(const uint8_t* x, const float* w, float* y, long long bpc, int NB, int A, int M, int S, int NT,
                    hipStream_t st) {
   const int nslabs = (NT + NTS - 1) / NTS;
@@ -747,7 +698,7 @@ int launch_persist(const uint8_t* x, const float* w, float* y, long long bpc, in
   const int n_cu = cu_count();
   const long long grid = std::min<long long>(nitems, xcd ? 2LL * n_cu / 8 * 8 : 2LL * n_cu);
   BF_REQUIRE(grid > 0 && (!xcd || grid % 8 == 0), "bf_beamform: persistent grid");
-  hipLaunchKernelGGL((beamform_table_persist_kernel<Signed, NTS, R, UPT, Mode, G>), dim3(static_cast<unsigned>(grid)),
+  hipLaunchKernelGGL((beamform_table_persist_kernel<Signed, NTS, R, UPT, G>), dim3(static_cast<unsigned>(grid)),
                      dim3(kThreads), lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd, nitems);
   BF_LAUNCHED("beamform_table_persist_kernel");
 }
@@ -782,7 +733,7 @@ int dispatch_table(const uint8_t* x, const float* w, float* y, long long bpc, in
   // 4 waves per item (256 VGPRs, two workgroups per CU), spill-free in the one-loop form: 791 us at config 4 against
   // 853 for the 8-wave form (128 VGPRs, spills 24-40 B/lane) and 933 for the 8-wave form bounded to 3 waves per
   // SIMD (no spill, one workgroup per CU), profiles/r4_s_table_os_ab.txt
-  if (table_os_fits(NB, A, M, x, w)) return launch_table_os<Signed, 0, 4>(x, w, y, bpc, A, st);
+  if (table_os_fits(NB, A, M, x, w)) return launch_table_os<Signed, 4>(x, w, y, bpc, A, st);
   // Long rows (>= 16 k-steps: 256+ antennas): the widest slab whose staged fragments leave room for a second
   // workgroup per CU, so one workgroup's table staging overlaps the other's contraction (cfg4: a 128 KiB slab held
   // one workgroup per CU and ran 3.1 ms); the slabs' re-reads of x hit L2 (XCD-grouped slabs).

@@ -26,28 +26,9 @@ namespace bf {
 
 constexpr int kGroup = 4;  // k-steps per register-resident load group (64 antennas)
 
-// Ablation bits for the diagnostic build (tools/diag_fused.py); the product instantiates Mode = 0 only.
-constexpr int kSkipCoef = 1, kSkipMfma = 2, kSkipStore = 4, kSkipLoad = 8;
-// Cache-policy bits for measurement: the product streams voltages with non-temporal loads (read once: -1.8 %
-// time, profiles/r1_v2_ablation_nt.txt); kCachedLoad selects plain loads, kNtStore non-temporal beam stores
-// (slower: +17 %).
-constexpr int kCachedLoad = 128, kNtStore = 256, kMapChannelFastF32 = 512, kMapBatchFastF32 = 1024,
-              kMapXcdBatchF32 = 2048;
-// Integer item kernel layout variants (A/B-measured in the diagnostic build, profiles/r1_v7_i8_variants.txt):
-// kSerialCoef evaluates the fast Q14 phasors one at a time (fewer live float64 temporaries: no gain), kPolOrder
-// restores the pol-outermost contraction of full slabs (the product runs sample-row-outermost with immediate
-// requantisation: -1.3 % at 3 waves per SIMD).
-constexpr int kSerialCoef = 1024, kPolOrder = 2048;
-// Cache-policy variants of the integer item kernel (which streams with non-temporal loads and stores).
-constexpr int kI8PlainStore = 8192, kI8PlainLoad = 16384;
-// Wave-priority variants (s_setprio 3): while issuing the item's loads / during the store phase.
-constexpr int kPrioLoads = 1 << 16, kPrioStores = 1 << 17;
-// Workgroup order variant: consecutive workgroups take consecutive batches of a channel instead of channels.
-constexpr int kMapBatchFast = 1 << 18, kMapXcdBatch = 1 << 19, kMapXcdRange = 1 << 20, kMapChannelFast = 1 << 21,
-              kMapXcdFlat = 1 << 22, kMapXcdBlock = 1 << 23;
-// Float-beam store variant: each wave's 8 KiB (64 rows x 128 B, one slab = the whole row) staged through a padded
-// wave-private LDS image and written as 1 KiB contiguous pieces per store instruction.
-constexpr int kLdsStoreF32 = 1 << 25;
+// Staged float-beam stores (the item kernel's StagedF32 form): each wave's 8 KiB (64 rows x 128 B, one slab = the
+// whole row) staged through a padded wave-private LDS image and written as 1 KiB contiguous pieces per store
+// instruction.
 constexpr int kF32StageRow = 36;                        // floats per staged row (32 + 4: 4-way write conflicts)
 constexpr size_t kF32StageBytes = 4 * 64 * kF32StageRow * 4;  // 4 waves x 64 rows
 
@@ -132,7 +113,9 @@ __device__ __forceinline__ void load_delays(CoefPrefetch<NTS>& cp, const FusedAr
   }
 }
 
-template <bool Exact, int Mode, int NTS>
+// OwnCopy is not read.  The item kernel's StagedF32 form passes true, which keeps its copy of this function an
+// instantiation of its own: sharing the other kernels' copy, hipcc pairs these LDS writes differently in that kernel.
+template <bool Exact, int NTS, bool OwnCopy = false>
 __device__ __forceinline__ void make_coefs(_Float16* lh, const CoefPrefetch<NTS>& cp, const FusedArgs& P, int b, int c,
                                            int tau0, int nts, int tid) {
   const double dt = P.t0 + static_cast<double>(b) * P.batch_dt;
@@ -147,15 +130,12 @@ __device__ __forceinline__ void make_coefs(_Float16* lh, const CoefPrefetch<NTS>
     const int a = e / nbeam, ml = e - a * nbeam;
     const int m = tau0 * 8 + ml;
     float re = 0.0f, im = 0.0f;
-    if constexpr (Mode & kSkipCoef) {
-      re = 0.5f + 1e-3f * a;
-      im = 0.25f - 1e-3f * m;
-    } else if (a < P.A && m < P.M) {
+    if (a < P.A && m < P.M) {
       if constexpr (Exact) {
         steering_coeff(cp.dv[j], ch, make_phase(P.ctot, P.ts), dt, &re, &im);
       } else {
         // hardware v_sin / v_cos on float64-reduced revolutions (<= 3.2 x 2^-24 from the float64 phasor), as the
-        // wide kernel since round 4: fewer VALU than the float32 polynomials of steering_coeff_fast
+        // wide kernel since round 4: fewer VALU than the float32 polynomial phasor it replaced
         steering_coeff_hw(cp.dv[j], chc, P.k, dt, &re, &im);
       }
       if (P.gain) apply_gain(cp.g[j], &re, &im);
@@ -308,9 +288,12 @@ __device__ void store_f32acc_i8_rows(const FusedArgs& P, int b, int c, int p, in
 // at this register footprint (the hardware interleaves their phases).
 // Pow2 (int8 beams): out_scale is a power of two, so RN(y * s) is exact and the requantisation's multiply and magic
 // add are one exact FMA (as requant_bits<true>).
-template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, int Mode = 0, int Occ = 1, bool Pow2 = false>
+// StagedF32 (float32 beams of a full 32-column slab that is the whole row, M == 16): the beams leave through the
+// LDS stage above as 1 KiB non-temporal stores; its store_pol is the non-temporal flavour.
+// The voltages stream with non-temporal loads (read once: -1.8 % time, profiles/r1_v2_ablation_nt.txt).
+template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32 = false, int Occ = 1,
+          bool Pow2 = false>
 __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_item_kernel(FusedArgs P) {
-  static_assert((Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -320,40 +303,19 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_item_kernel(Fuse
   const size_t ant_stride = static_cast<size_t>(P.C) * P.T * 4;
   const int item = blockIdx.x;
   int b, c;
-  if constexpr ((Mode & kMapChannelFastF32) != 0) {  // diagnostics: the earlier channel-fastest order
-    c = item % P.C;
-    b = (item / P.C) % P.B;
-  } else if constexpr ((Mode & kMapBatchFastF32) != 0) {  // diagnostics: batch fastest
-    c = (item / P.B) % P.C;
-    b = item % P.B;
-  } else if constexpr ((Mode & kMapXcdBatchF32) != 0) {  // diagnostics: XCD x -> channels == x mod 8, batch fastest
-    const int xcd = item & 7, local = (item >> 3) % (P.B * (P.C >> 3));
-    b = local % P.B;
-    c = (local / P.B) * 8 + xcd;
-  } else {
-    item_coords(item, P.C, P.B, P.xcd_order != 0, &b, &c);
-  }
+  item_coords(item, P.C, P.B, P.xcd_order != 0, &b, &c);
   const int slab = item / (P.C * P.B);
   const int tau0 = slab * NTS;
   const int nts = Full ? NTS : min(NTS, P.NT - tau0);
 
   uint32_t d[kGroup][4][4];
   CoefPrefetch<NTS> cp;
-  if constexpr (!(Mode & kSkipCoef)) load_delays<NTS>(cp, P, c, tau0, nts, tid);
+  load_delays<NTS>(cp, P, c, tau0, nts, tid);
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (Mode & kSkipLoad) {
-#pragma unroll
-    for (int ss = 0; ss < kGroup; ++ss)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) d[ss][q][j] = static_cast<uint32_t>(tid * 0x01010101u + ss + q + j);
-  } else {
-    const uint8_t* base = P.raw + (static_cast<size_t>(b) * P.A * P.C + c) * static_cast<size_t>(P.T) * 4;
-    load_group<(Mode & kCachedLoad) == 0>(base, ant_stride, tq, T4, 0, P.A, h, d);
-  }
+  const uint8_t* base = P.raw + (static_cast<size_t>(b) * P.A * P.C + c) * static_cast<size_t>(P.T) * 4;
+  load_group<true>(base, ant_stride, tq, T4, 0, P.A, h, d);
   __builtin_amdgcn_sched_barrier(0);
-  make_coefs<Exact, Mode, NTS>(reinterpret_cast<_Float16*>(lds), cp, P, b, c, tau0, nts, tid);
+  make_coefs<Exact, NTS, StagedF32>(reinterpret_cast<_Float16*>(lds), cp, P, b, c, tau0, nts, tid);
   __syncthreads();
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
@@ -362,55 +324,34 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_item_kernel(Fuse
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int tau = 0; tau < NTS; ++tau) acc[i][tau] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (Mode & kSkipMfma) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][0][q] = __builtin_bit_cast(float, d[q][p + 1][i] ^ d[q][p][i]);
+    if (p == 0) {
+      contract_pol<Signed, NTS, Full, true>(lds, 0, P.S, nts, lane, 0, d, acc);
     } else {
-      if (p == 0) {
-        contract_pol<Signed, NTS, Full, true>(lds, 0, P.S, nts, lane, 0, d, acc);
-      } else {
-        contract_pol<Signed, NTS, Full, false>(lds, 0, P.S, nts, lane, 1, d, acc);
-      }
+      contract_pol<Signed, NTS, Full, false>(lds, 0, P.S, nts, lane, 1, d, acc);
     }
-    if constexpr (Mode & kSkipStore) {
-      float sum = 0.f;
+    if constexpr (OutI8 && Full) {
+      store_f32acc_i8_rows<NTS, Pow2>(P, b, c, p, tau0, tq, h, lane, wave, tv, acc);
+    } else if constexpr (!OutI8 && Full && NTS == 2 && StagedF32) {
+      // M2 == 32 (launcher): the wave's rows 64 w .. 64 w + 63 of (b, p, c) are one contiguous 8 KiB run
+      float* stg = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + static_cast<size_t>(P.S) * NTS * 2 * 64 * 16) +
+                   wave * 64 * kF32StageRow;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int tau = 0; tau < NTS; ++tau) sum += acc[i][tau][0] + acc[i][tau][1] + acc[i][tau][2] + acc[i][tau][3];
-      if (sum == 1234.5f) reinterpret_cast<float*>(P.y)[tid] = sum;
-    } else {
-      if constexpr (OutI8 && Full) {
-        store_f32acc_i8_rows<NTS, Pow2>(P, b, c, p, tau0, tq, h, lane, wave, tv, acc);
-      } else if constexpr (!OutI8 && Full && NTS == 2 && (Mode & kLdsStoreF32) != 0) {
-        // M2 == 32 (launcher): the wave's rows 64 w .. 64 w + 63 of (b, p, c) are one contiguous 8 KiB run
-        float* stg = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + static_cast<size_t>(P.S) * NTS * 2 * 64 * 16) +
-                     wave * 64 * kF32StageRow;
+        for (int tau = 0; tau < 2; ++tau)
+          *reinterpret_cast<f32x4*>(stg + (4 * tl + i) * kF32StageRow + 16 * tau + 4 * h) = acc[i][tau];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const size_t orow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T) + 64 * wave;
+      float* o = reinterpret_cast<float*>(P.y) + orow * 32;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int tau = 0; tau < 2; ++tau)
-            *reinterpret_cast<f32x4*>(stg + (4 * tl + i) * kF32StageRow + 16 * tau + 4 * h) = acc[i][tau];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const size_t orow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T) + 64 * wave;
-        float* o = reinterpret_cast<float*>(P.y) + orow * 32;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int row = 8 * k + (lane >> 3), c4 = lane & 7;  // 16-byte piece `lane` of the k-th KiB
-          const f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * kF32StageRow + 4 * c4);
-          if (64 * wave + row < P.T) {
-            if constexpr ((Mode & kNtStore) != 0)
-              __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o + 256 * k + 4 * lane));
-            else
-              *reinterpret_cast<f32x4*>(o + 256 * k + 4 * lane) = v;
-          }
-        }
-      } else if (tv) {
-        store_pol<OutI8, NTS, Full, (Mode & kNtStore) != 0>(P, b, c, p, tau0, nts, tq, h, acc);
+      for (int k = 0; k < 8; ++k) {
+        const int row = 8 * k + (lane >> 3), c4 = lane & 7;  // 16-byte piece `lane` of the k-th KiB
+        const f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * kF32StageRow + 4 * c4);
+        if (64 * wave + row < P.T) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(o + 256 * k + 4 * lane));
       }
+    } else if (tv) {
+      store_pol<OutI8, NTS, Full, StagedF32>(P, b, c, p, tau0, nts, tq, h, acc);
     }
   }
 }
@@ -452,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void beamform_fused_kernel(FusedArgs P) {
     __builtin_amdgcn_sched_barrier(0);
     if (chunk < nchunks) load_group(base, ant_stride, chunk * 16 + tl, T4, 0, P.A, h, d);
     __builtin_amdgcn_sched_barrier(0);
-    make_coefs<Exact, 0, NTS>(reinterpret_cast<_Float16*>(lds), cp, P, b, c, tau0, nts, tid);
+    make_coefs<Exact, NTS>(reinterpret_cast<_Float16*>(lds), cp, P, b, c, tau0, nts, tid);
   } else {
     if (chunk < nchunks) load_group(base, ant_stride, chunk * 16 + tl, T4, 0, P.A, h, d);
     gen_coefs<Exact>(reinterpret_cast<_Float16*>(lds), P, b, c, tau0, nts, tid);
@@ -665,18 +606,12 @@ __device__ __forceinline__ uint32_t requant4(const i32x4_t& acc, const int* cols
 }
 
 
-template <int Mode>
-__device__ __forceinline__ void st_i8(u32x4_t v, u32x4_t* p) {
-  if constexpr (Mode & kI8PlainStore)
-    *p = v;
-  else
-    __builtin_nontemporal_store(v, p);
-}
+// The integer item kernel streams: non-temporal stores (and loads).
+__device__ __forceinline__ void st_i8(u32x4_t v, u32x4_t* p) { __builtin_nontemporal_store(v, p); }
 
 // The item's Q14 coefficient table: exact-contract phasors of this thread's (antenna, beam) pairs (fast + fixup) ->
 // hi/lo int8 limb fragments in LDS (coef8_byte layout) + the per-wave column sums of the unsigned correction.
-// Mode (diagnostics): kSkipCoef synthetic values, 16 float32 phasors only (inexact), 128 exact only, kSerialCoef.
-template <bool Signed, int NTS, int Mode>
+template <bool Signed, int NTS>
 __device__ __forceinline__ void i8_coef_phase(int8_t* lb, int* colsum, const CoefPrefetch<NTS>& cp, const FusedArgs& P,
                                               int b, int c, int tau0, int nts, int S8, int tid, int lane, int wave) {
   const double dt = P.t0 + static_cast<double>(b) * P.batch_dt;
@@ -694,24 +629,7 @@ __device__ __forceinline__ void i8_coef_phase(int8_t* lb, int* colsum, const Coe
     const int a = e / nbeam, m = tau0 * 8 + (e - a * nbeam);
     valid[j] = e < npairs && a < P.A && m < P.M;
   }
-  if constexpr (Mode & kSkipCoef) {
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      wc[j] = 8192 + 16 * j + tid;
-      ws[j] = 4096 - 16 * j;
-    }
-  } else if constexpr (Mode & 16) {  // diagnostics: float32 phasors only (not the contract)
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      float re, im;
-      steering_coeff_fast(cp.dv[j], ch - P.ctot / 2.0, P.k, dt, &re, &im);
-      wc[j] = static_cast<int>(__builtin_rintf(re * 16384.0f));
-      ws[j] = static_cast<int>(__builtin_rintf(im * 16384.0f));
-    }
-  } else {
-    q14_coeffs<NP, !(Mode & 128), (Mode & kSerialCoef) != 0>(cp.dv, cp.g, valid, ch, P.ctot, P.ts, P.k, dt,
-                                                               P.gain, wc, ws);
-  }
+  q14_coeffs<NP>(cp.dv, cp.g, valid, ch, P.ctot, P.ts, P.k, dt, P.gain, wc, ws);
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
     const int e = tid + j * kThreads;
@@ -751,7 +669,8 @@ __device__ __forceinline__ void i8_coef_phase(int8_t* lb, int* colsum, const Coe
 }
 
 // Full-slab contraction: sample row i outermost, both pols inside, each 4-MFMA chain (hi limbs, << 8, lo limbs)
-// requantised at once into packed int8 columns pkall[p][tau][i] (lane (tl, h): row 4 tq + i, columns 16 tau + 4 h ..).
+// requantised at once into packed int8 columns pkall[p][tau][i] (lane (tl, h): row 4 tq + i, columns 16 tau + 4 h ..):
+// -1.3 % at 3 waves per SIMD against the pol-outermost order (profiles/r1_v7_i8_variants.txt).
 template <bool Signed, int NTS, bool Pow2 = false>
 __device__ __forceinline__ void i8_contract_rows(const int4* fr, const uint32_t (&d)[2][8][4], const int* colsum,
                                                  float s32, int S8, int lane, int h, uint32_t (&pkall)[2][NTS][4]) {
@@ -806,7 +725,7 @@ __device__ __forceinline__ void i8_contract_rows(const int4* fr, const uint32_t 
 // A wave's 64 output rows of a full-width slab (M2 == 16 NTS) are one contiguous 1-2 KiB block: after the row
 // transpose lane (tl, h) holds row 4 tl + h; ds_bpermute the row-per-lane chunks so that store instruction si
 // writes bytes [1024 si, 1024 si + 1024) of the block.  rows = valid rows of the block (T - 64 wave).
-template <int NTS, int Mode>
+template <int NTS>
 __device__ __forceinline__ void i8_store_block(const uint32_t (&pk)[NTS][4], int8_t* block, int lane, int rows) {
 #pragma unroll
   for (int si = 0; si < NTS; ++si) {
@@ -822,7 +741,7 @@ __device__ __forceinline__ void i8_store_block(const uint32_t (&pk)[NTS][4], int
         w[j] = ch ? w1 : w[j];
       }
     }
-    if (r < rows) st_i8<Mode>(u32x4_t{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4_t*>(block + 16 * lane + 1024 * si));
+    if (r < rows) st_i8(u32x4_t{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4_t*>(block + 16 * lane + 1024 * si));
   }
 }
 
@@ -860,14 +779,14 @@ __device__ void store_f32acc_i8_rows(const FusedArgs& P, int b, int c, int p, in
   }
   const size_t prow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T);
   if (M2 == 16 * NTS) {
-    i8_store_block<NTS, 0>(pk, reinterpret_cast<int8_t*>(P.y) + (prow + 64 * wave) * M2, lane, P.T - 64 * wave);
+    i8_store_block<NTS>(pk, reinterpret_cast<int8_t*>(P.y) + (prow + 64 * wave) * M2, lane, P.T - 64 * wave);
     return;
   }
   if (tv) {
     int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 4 * tq + h) * M2 + 16 * tau0;
 #pragma unroll
     for (int tau = 0; tau < NTS; ++tau)
-      st_i8<0>(u32x4_t{pk[tau][0], pk[tau][1], pk[tau][2], pk[tau][3]}, reinterpret_cast<u32x4_t*>(o + 16 * tau));
+      st_i8(u32x4_t{pk[tau][0], pk[tau][1], pk[tau][2], pk[tau][3]}, reinterpret_cast<u32x4_t*>(o + 16 * tau));
   }
 }
 
@@ -876,14 +795,10 @@ __device__ void store_f32acc_i8_rows(const FusedArgs& P, int b, int c, int p, in
 // coefficients + Q14 limbs under them -> barrier -> full slabs: sample row outermost, both pols, 4 i8 MFMAs per
 // (row, pol, tile) requantised at once, row transpose + ds_bpermute into 1 KiB store blocks; partial slabs and
 // one/two beams: the per-pol path below.  3 waves per SIMD (launch bound; 4 spills).
-// Mode (diagnostics only): kSkipCoef / kSkipMfma / kSkipStore / kSkipLoad as the float item kernel; 16 = fast
-// (f32 sincos) coefficients only (inexact); 128 = exact coefficients only (no fast attempt); the layout, cache
-// policy, priority and workgroup-order variants defined above.
 // A64: exactly 64 antennas and every in-item offset below 2^32 (the launcher checks), so no antenna is clamped.
 // Pow2: out_scale * 2^-14 is a power of two (requant_bits<true>: one exact FMA).
-template <bool Signed, int NTS, bool Full, int Mode = 0, int Occ = 3, bool A64 = false, bool Pow2 = false>
+template <bool Signed, int NTS, bool Full, int Occ = 3, bool A64 = false, bool Pow2 = false>
 __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(FusedArgs P) {
-  static_assert((Mode & (kSkipCoef | kSkipMfma | kSkipStore | kSkipLoad)) == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) half8 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -893,37 +808,8 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
   const int tqc = tv ? tq : T4 - 1;
   const size_t ant_stride = static_cast<size_t>(P.C) * P.T * 4;
   const int item = blockIdx.x;
-  // item -> (b, c): XCD-range order (item_coords); diagnostics: kMapChannelFast (channel fastest, the earlier
-  // order), kMapBatchFast (batch fastest), kMapXcdBatch (XCD x: channels == x mod 8, batch fastest), kMapXcdRange
-  // (XCD-range, batch fastest)
   int c, b;
-  if constexpr ((Mode & kMapXcdRange) != 0) {
-    const int xcd = item & 7, local = (item >> 3) % (P.B * (P.C >> 3));
-    b = local % P.B;
-    c = xcd * (P.C >> 3) + local / P.B;
-  } else if constexpr ((Mode & kMapXcdBlock) != 0) {  // XCD x: 64-channel blocks x, x + 8, ... (C % 512 == 0)
-    const int xcd = item & 7, local = (item >> 3) % (P.B * (P.C >> 3));
-    const int cl = local % (P.C >> 3);
-    b = local / (P.C >> 3);
-    c = ((cl >> 6) * 8 + xcd) * 64 + (cl & 63);
-  } else if constexpr ((Mode & kMapXcdFlat) != 0) {  // XCD x: items [x B C/8, (x+1) B C/8) of the (b, c) order
-    const int xcd = item & 7, local = (item >> 3) % (P.B * (P.C >> 3));
-    const int flat = xcd * (P.B * (P.C >> 3)) + local;
-    b = flat / P.C;
-    c = flat % P.C;
-  } else if constexpr ((Mode & kMapXcdBatch) != 0) {
-    const int xcd = item & 7, local = (item >> 3) % (P.B * (P.C >> 3));
-    b = local % P.B;
-    c = (local / P.B) * 8 + xcd;
-  } else if constexpr ((Mode & kMapBatchFast) != 0) {
-    c = (item / P.B) % P.C;
-    b = item % P.B;
-  } else if constexpr ((Mode & kMapChannelFast) != 0) {
-    c = item % P.C;
-    b = (item / P.C) % P.B;
-  } else {
-    item_coords(item, P.C, P.B, P.xcd_order != 0, &b, &c);
-  }
+  item_coords(item, P.C, P.B, P.xcd_order != 0, &b, &c);
   const int slab = item / (P.C * P.B);
   const int tau0 = slab * NTS;
   const int nts = Full ? NTS : min(NTS, P.NT - tau0);
@@ -933,22 +819,14 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
   int* colsum = reinterpret_cast<int*>(lb + static_cast<size_t>(2) * NTS * 2 * 64 * 16);
 
   // 1. delay model (oldest), 2. voltages, 3. coefficients under them
-  if constexpr ((Mode & kPrioLoads) != 0) __builtin_amdgcn_s_setprio(3);
   CoefPrefetch<NTS> cp;
-  if constexpr (!(Mode & kSkipCoef)) load_delays<NTS>(cp, P, c, tau0, nts, tid);
+  load_delays<NTS>(cp, P, c, tau0, nts, tid);
   __builtin_amdgcn_sched_barrier(0);
   const uint8_t* base = P.raw + (static_cast<size_t>(b) * P.A * P.C + c) * static_cast<size_t>(P.T) * 4;
   const uint32_t loff64 = static_cast<uint32_t>(8 * h) * static_cast<uint32_t>(ant_stride) + tqc * 16u;  // A64 only
   uint32_t d[2][8][4];
 #pragma unroll
   for (int ss = 0; ss < 2; ++ss) {
-    if constexpr (Mode & kSkipLoad) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) d[ss][q][jj] = static_cast<uint32_t>(tid * 0x01010101u + ss + q + jj);
-      continue;
-    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const u32x4_t* src;
@@ -959,7 +837,7 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
         a = a < P.A ? a : P.A - 1;
         src = reinterpret_cast<const u32x4_t*>(base + static_cast<size_t>(a) * ant_stride + tqc * 16u);
       }
-      const u32x4_t v = (Mode & kI8PlainLoad) ? *src : __builtin_nontemporal_load(src);
+      const u32x4_t v = __builtin_nontemporal_load(src);
       d[ss][q][0] = v[0];
       d[ss][q][1] = v[1];
       d[ss][q][2] = v[2];
@@ -967,18 +845,15 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr ((Mode & kPrioLoads) != 0) __builtin_amdgcn_s_setprio(0);
-  i8_coef_phase<Signed, NTS, Mode>(lb, colsum, cp, P, b, c, tau0, nts, S8, tid, lane, wave);
+  i8_coef_phase<Signed, NTS>(lb, colsum, cp, P, b, c, tau0, nts, S8, tid, lane, wave);
   __syncthreads();
   const int4* fr = reinterpret_cast<const int4*>(lds);
   const float s32 = P.out_scale * 0x1p-14f;
 
   // Full slabs: sample row i outermost, both pols inside, each 4-MFMA chain requantised at once, so only the
   // packed bytes (16 VGPRs) stay live and the voltage registers of row i die after it.
-  constexpr bool kTile = Full && !(Mode & (kSkipMfma | kSkipStore | kSkipLoad | kPolOrder));
   uint32_t pkall[2][NTS][4];
-  if constexpr (kTile) i8_contract_rows<Signed, NTS, Pow2>(fr, d, colsum, s32, S8, lane, h, pkall);
-  if constexpr ((Mode & kPrioStores) != 0) __builtin_amdgcn_s_setprio(3);
+  if constexpr (Full) i8_contract_rows<Signed, NTS, Pow2>(fr, d, colsum, s32, S8, lane, h, pkall);
 
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
@@ -986,7 +861,7 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
     i32x4_t acc[4][NTS];
 #pragma unroll
     for (int tau = 0; tau < NTS; ++tau) {
-      if constexpr (kTile) break;
+      if constexpr (Full) break;  // (contracted above)
       if (!Full && tau >= nts) break;
       i32x4_t chi[2], clo[2];
 #pragma unroll
@@ -1002,16 +877,6 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if constexpr (Mode & kSkipMfma) {
-          uint32_t x = static_cast<uint32_t>(chi[0][i] ^ clo[1][i]) + p;
-#pragma unroll
-          for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) x = (x ^ d[ss][q][i]) + q;  // every load stays live
-          acc[i][tau] = i32x4_t{static_cast<int>(x), static_cast<int>(x >> 3), static_cast<int>(x >> 5),
-                                static_cast<int>(x >> 7)};
-          continue;
-        }
         i32x4_t f[2];
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
@@ -1035,35 +900,21 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
         acc[i][tau] = mfma_i8(clo[1], f[1], t);
       }
     }
-    if constexpr (Full && !(Mode & kSkipStore)) {
-      // requantise, then a 4x4 transpose across the lane groups h (v_permlane32/16_swap) so lane (tl, h) holds
+    if constexpr (Full) {
+      // the requantised columns, then a 4x4 transpose across the lane groups h (v_permlane32/16_swap) so lane (tl, h) holds
       // all 16 * NTS bytes of output row 4 tq + h: a wave's 64 rows x 32 B go out as 2 KB of 16-B stores.
       uint32_t pk[NTS][4];
 #pragma unroll
       for (int tau = 0; tau < NTS; ++tau) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if constexpr (kTile)
-            pk[tau][i] = pkall[p][tau][i];
-          else
-            pk[tau][i] = requant4<Signed, Pow2>(acc[i][tau], colsum, 16 * tau + 4 * h, s32);
-        }
+        for (int i = 0; i < 4; ++i) pk[tau][i] = pkall[p][tau][i];
         transpose_rows4(pk[tau]);
-      }
-      if constexpr (Mode & 32) {  // diagnostics: contiguous 1 KB per store instruction (timing only, wrong data)
-        const size_t orow0 = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T) + 64 * wave;
-        int8_t* o = reinterpret_cast<int8_t*>(P.y) + orow0 * M2 + 16 * lane;
-#pragma unroll
-        for (int tau = 0; tau < NTS; ++tau)
-          __builtin_nontemporal_store(u32x4_t{pk[tau][0], pk[tau][1], pk[tau][2], pk[tau][3]},
-                                      reinterpret_cast<u32x4_t*>(o + 1024 * tau));
-        continue;
       }
       if (M2 == 16 * NTS) {
         // the slab is the whole row, so the wave's 64 rows are one contiguous 1-2 KB block: ds_bpermute the
         // row-per-lane chunks so that store instruction s writes bytes [1024 s, 1024 s + 1024) of it.
         const size_t orow0 = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T) + 64 * wave;
-        i8_store_block<NTS, Mode>(pk, reinterpret_cast<int8_t*>(P.y) + orow0 * M2, lane, P.T - 64 * wave);
+        i8_store_block<NTS>(pk, reinterpret_cast<int8_t*>(P.y) + orow0 * M2, lane, P.T - 64 * wave);
         continue;
       }
       if (tv) {
@@ -1071,20 +922,11 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
         int8_t* o = reinterpret_cast<int8_t*>(P.y) + orow * M2 + 16 * tau0;
 #pragma unroll
         for (int tau = 0; tau < NTS; ++tau)
-          st_i8<Mode>(u32x4_t{pk[tau][0], pk[tau][1], pk[tau][2], pk[tau][3]}, reinterpret_cast<u32x4_t*>(o + 16 * tau));
+          st_i8(u32x4_t{pk[tau][0], pk[tau][1], pk[tau][2], pk[tau][3]}, reinterpret_cast<u32x4_t*>(o + 16 * tau));
       }
       continue;
     }
     if (!tv) continue;
-    if constexpr (Mode & kSkipStore) {
-      int sum = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int tau = 0; tau < NTS; ++tau) sum += acc[i][tau][0] ^ acc[i][tau][1] ^ acc[i][tau][2] ^ acc[i][tau][3];
-      if (sum == 0x12345678) reinterpret_cast<int*>(P.y)[tid] = sum;
-      continue;
-    }
     if constexpr (NTS == 1) {
       if (M2 == 2 || M2 == 4) {
         // one or two beams (config 2): lane (tl, h = 0) holds every column of rows 4 tq .. 4 tq + 3, which are
@@ -1100,7 +942,7 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
                                                 __builtin_amdgcn_perm(pk[3], pk[2], 0x05040100u)},
                                         reinterpret_cast<u32x2_t*>(o));
           else
-            st_i8<Mode>(u32x4_t{pk[0], pk[1], pk[2], pk[3]}, reinterpret_cast<u32x4_t*>(o));
+            st_i8(u32x4_t{pk[0], pk[1], pk[2], pk[3]}, reinterpret_cast<u32x4_t*>(o));
         }
         continue;
       }
@@ -1135,7 +977,7 @@ bool item_xcd_order(const FusedArgs& P) {
   return (P.C & 7) == 0 && P.M >= 8;
 }
 
-template <bool Signed, int NTS, bool Full, int Mode = 0, int Occ = 3>
+template <bool Signed, int NTS, bool Full, int Occ = 3>
 int launch_i8_item(FusedArgs P, hipStream_t st, size_t min_lds = 0) {
   P.nslabs = (P.NT + NTS - 1) / NTS;
   P.xcd_order = item_xcd_order(P);
@@ -1146,13 +988,13 @@ int launch_i8_item(FusedArgs P, hipStream_t st, size_t min_lds = 0) {
   const bool pow2 = scale_is_pow2(P.out_scale * 0x1p-14f);  // the requantisation's exact single FMA
   const dim3 grid(static_cast<unsigned>(n_items)), block(kThreads);
   if (a64 && pow2)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Mode, Occ, true, true>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, true, true>), grid, block, lds, st, P);
   else if (a64)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Mode, Occ, true, false>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, true, false>), grid, block, lds, st, P);
   else if (pow2)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Mode, Occ, false, true>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, true>), grid, block, lds, st, P);
   else
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Mode, Occ, false, false>), grid, block, lds, st, P);
+    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, false>), grid, block, lds, st, P);
   BF_LAUNCHED("beamform_fused_i8_item_kernel");
 }
 
@@ -1191,28 +1033,28 @@ int launch_i8(FusedArgs P, hipStream_t st) {
   BF_LAUNCHED("beamform_fused_i8_kernel");
 }
 
-template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, int Mode, int Occ, bool Pow2>
+template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32, int Occ, bool Pow2>
 int launch_item_k(FusedArgs P, hipStream_t st) {
   P.nslabs = (P.NT + NTS - 1) / NTS;
   P.xcd_order = item_xcd_order(P);
-  if constexpr ((Mode & kLdsStoreF32) != 0)
+  if constexpr (StagedF32)
     BF_REQUIRE(!OutI8 && Full && NTS == 2 && P.M == 16 && P.T <= 256, "item kernel: staged f32 stores need M == 16");
-  const size_t lds = coef_lds_bytes(P.S, NTS) + ((Mode & kLdsStoreF32) ? kF32StageBytes : 0);
+  const size_t lds = coef_lds_bytes(P.S, NTS) + (StagedF32 ? kF32StageBytes : 0);
   const long long n_items = static_cast<long long>(P.nslabs) * P.B * P.C;
   BF_REQUIRE(n_items < (1LL << 31), "bf_beamform_fused: too many (batch, channel) items");
-  hipLaunchKernelGGL((beamform_fused_item_kernel<Signed, OutI8, NTS, Exact, Full, Mode, Occ, Pow2>),
+  hipLaunchKernelGGL((beamform_fused_item_kernel<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, Pow2>),
                      dim3(static_cast<unsigned>(n_items)), dim3(kThreads), lds, st, P);
   BF_LAUNCHED("beamform_fused_item_kernel");
 }
 
-template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, int Mode = 0, int Occ = 1>
+template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32 = false, int Occ = 1>
 int launch_item(FusedArgs P, hipStream_t st) {
   if constexpr (OutI8) {
     // a power-of-two scale: the float path's requantisation as one exact FMA (its round-4 two-rounding form had
     // cost cfg3 int8-via-f32 ~3 %, BENCH_r03 460.8 -> BENCH_r04 476.3 us; A/B in DESIGN §5)
-    if (scale_is_pow2(P.out_scale)) return launch_item_k<Signed, OutI8, NTS, Exact, Full, Mode, Occ, true>(P, st);
+    if (scale_is_pow2(P.out_scale)) return launch_item_k<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, true>(P, st);
   }
-  return launch_item_k<Signed, OutI8, NTS, Exact, Full, Mode, Occ, false>(P, st);
+  return launch_item_k<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, false>(P, st);
 }
 
 template <bool Signed, bool OutI8, int NTS, bool Exact>
@@ -1247,12 +1089,12 @@ int dispatch(FusedArgs P, hipStream_t st) {
       // float beams of 16 beams (config 3): 1 KiB contiguous non-temporal stores staged through LDS, 807 -> 784 us
       // same process (profiles/r3_v_f32_staged_stores.txt, r3_x_f32_staged_ab.txt)
       if constexpr (!OutI8)
-        if (P.M == 16 && P.T <= 256) return launch_item<Signed, false, 2, Exact, true, kLdsStoreF32 | kNtStore>(P, st);
-      if (M2 % 32 == 0) return launch_item<Signed, OutI8, 2, Exact, true, 0, kOcc>(P, st);
-      return launch_item<Signed, OutI8, 2, Exact, false, 0, kOcc>(P, st);
+        if (P.M == 16 && P.T <= 256) return launch_item<Signed, false, 2, Exact, true, true>(P, st);
+      if (M2 % 32 == 0) return launch_item<Signed, OutI8, 2, Exact, true, false, kOcc>(P, st);
+      return launch_item<Signed, OutI8, 2, Exact, false, false, kOcc>(P, st);
     }
-    if (M2 == 16) return launch_item<Signed, OutI8, 1, Exact, true, 0, kOcc>(P, st);
-    return launch_item<Signed, OutI8, 1, Exact, false, 0, kOcc>(P, st);
+    if (M2 == 16) return launch_item<Signed, OutI8, 1, Exact, true, false, kOcc>(P, st);
+    return launch_item<Signed, OutI8, 1, Exact, false, false, kOcc>(P, st);
   }
   const int want = 2;  // the generic kernel's widest slab
   if (want >= 4 && P.NT >= 4 && coef_lds_bytes(P.S, 4) <= kMaxLds) return launch_generic<Signed, OutI8, 4, Exact>(P, st);

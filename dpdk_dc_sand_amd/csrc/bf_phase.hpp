@@ -83,42 +83,8 @@ __device__ __forceinline__ void steering_coeff(float4 dv, double ch, const Phase
   *im = static_cast<float>(s);
 }
 
-// Fast steering phasor (fused kernels' default): rot = phi' + tau' * (ch - Ctot/2) * K with K = -pi/(Ctot*Ts)
-// precomputed on the host, in float64 (no divisions); reduced by pi/2 in float64 (Cody-Waite, two terms); then
-// float32 minimax polynomials (Cephes sinf/cosf coefficients) on the reduced angle rf in [-pi/4, pi/4], a
-// first-order correction for rf's float32 rounding dr = r - rf, and the quadrant swap.  <= 1.32 ulp of float32 (mean
-// |error| 2e-8) against the exact phasor over 2e7 probe angles (tools/probes/sincosf_check.c), about a third of the
-// instructions of the generic sincosf (which redoes a general range reduction).
-// Returns the float64 rotation (callers that need a validity range check it).
-__device__ __forceinline__ double steering_coeff_fast(float4 dv, double chc, double k, double dt, float* re,
-                                                      float* im) {
-  double tau = static_cast<double>(dv.x);
-  double phi = static_cast<double>(dv.z);
-  if (dt != 0.0) {
-    tau = fma(static_cast<double>(dv.y), dt, tau);
-    phi = fma(static_cast<double>(dv.w), dt, phi);
-  }
-  const double rot = fma(tau * chc, k, phi);
-  const double n = rint(rot * 0.63661977236758138);  // 2 / pi
-  double r = fma(-n, 1.5707963267948966e+00, rot);
-  r = fma(-n, 6.123233995736766e-17, r);
-  const float rf = static_cast<float>(r);
-  const float dr = static_cast<float>(r - static_cast<double>(rf));
-  const float z = rf * rf;
-  const float ps = fmaf(fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f), z * rf, rf);
-  const float pc = fmaf(fmaf(fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f),
-                             z * z, -0.5f * z), 1.0f, 1.0f);
-  const float s1 = fmaf(pc, dr, ps), c1 = fmaf(-ps, dr, pc);  // sin, cos of r = rf + dr
-  // quadrant by one saturating v_cvt_i32_f64 (the 64-bit conversion costs four float64 instructions); exact for
-  // |n| < 2^31, i.e. |rot| < 3.4e9 rad, far beyond where a float64 rotation still carries phase information
-  const int q = __double2int_rn(n) & 3;
-  const float s0 = (q & 1) ? c1 : s1, c0 = (q & 1) ? s1 : c1;
-  *re = ((q + 1) & 2) ? -c0 : c0;
-  *im = (q & 2) ? -s0 : s0;
-  return rot;
-}
-
-// Hardware phasor (measurement): the float64 rotation reduced to revolutions in float64 (u = rot / 2 pi - rint(.),
+// Hardware phasor (the fused kernels' default): rot = phi' + tau' * (ch - Ctot/2) * K with K = -pi/(Ctot*Ts)
+// precomputed on the host, in float64 (no divisions), reduced to revolutions in float64 (u = rot / 2 pi - rint(.),
 // |u| <= 1/2), rounded once to float32, then v_sin_f32 / v_cos_f32 (which take revolutions).  The argument rounding
 // is <= 2^-26 rev (~2^-23.3 in the phasor); the instructions' own error is measured by
 // tools/probes/sincos_hw_probe.hip.
@@ -222,14 +188,11 @@ __device__ __forceinline__ void q14_exact(float4 dv, double ch, double ctot, dou
 }
 
 // N coefficients per lane: fast for all, then an exact pass per flagged coefficient (a wave runs as many exact
-// passes as its most-flagged lane has flags: usually none).  valid[j] false -> W = 0.  FastFirst = false is the
-// exact-only form (diagnostics / ablation).  Serial = true evaluates the N fast phasors one after another
-// (a scheduling barrier between them): less instruction-level parallelism, but the float64 temporaries of only one
-// phasor are live, which is what lets a kernel whose voltage loads are in flight meanwhile fit more waves.
+// passes as its most-flagged lane has flags: usually none).  valid[j] false -> W = 0.
 // Branchless = true evaluates every fast phasor (invalid ones on their clamped, finite inputs) and zeroes the
 // invalid results afterwards: no per-coefficient branch, so the N float64 Horner chains interleave (a lone wave per
 // SIMD is otherwise latency-bound on them).
-template <int N, bool FastFirst = true, bool Serial = false, bool Branchless = false>
+template <int N, bool Branchless = false>
 __device__ __forceinline__ void q14_coeffs(const float4 (&dv)[N], const float (&g)[N], const bool (&valid)[N],
                                            double ch, double ctot, double ts, double k, double dt, const float* gain,
                                            int (&wc)[N], int (&ws)[N]) {
@@ -239,7 +202,7 @@ __device__ __forceinline__ void q14_coeffs(const float4 (&dv)[N], const float (&
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     wc[j] = ws[j] = 0;
-    if constexpr (Branchless && FastFirst) {
+    if constexpr (Branchless) {
       int c, s;
       const bool ok = q14_fast(dv[j], chc, k, dt, uk, g[j] * 16384.0f, &c, &s);
       wc[j] = valid[j] ? c : 0;
@@ -248,12 +211,7 @@ __device__ __forceinline__ void q14_coeffs(const float4 (&dv)[N], const float (&
       continue;
     }
     if (!valid[j]) continue;
-    if constexpr (FastFirst) {
-      if (!q14_fast(dv[j], chc, k, dt, uk, g[j] * 16384.0f, &wc[j], &ws[j])) flagged |= 1u << j;
-    } else {
-      flagged |= 1u << j;
-    }
-    if constexpr (Serial) __builtin_amdgcn_sched_barrier(0);
+    if (!q14_fast(dv[j], chc, k, dt, uk, g[j] * 16384.0f, &wc[j], &ws[j])) flagged |= 1u << j;
   }
   while (flagged) {
     const int j = __builtin_ctz(flagged);

@@ -51,11 +51,8 @@ __device__ __forceinline__ bool w32_slot_antenna(int sa, int A, int* a) {
   return *a >= 32 * st && *a < A;
 }
 
-// Mode (diagnostics only): 1 the unit-gain walk without its stores (one store per thread if a sum is impossible),
-// 2 the stores without the walk (each word its channel index).
-template <bool Gain, int Mode = 0>
+template <bool Gain>
 __global__ __launch_bounds__(256) void q14_table_kernel(Q14TableArgs P) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   const int b = blockIdx.z;
   const int c0 = blockIdx.y * P.run;
   const int w = blockIdx.x * 256 + threadIdx.x;  // word within a (b, c[, slab]) block
@@ -140,20 +137,12 @@ __global__ __launch_bounds__(256) void q14_table_kernel(Q14TableArgs P) {
   auto pack = [](int wc, int ws) {  // (Wc & 0xffff) | Ws << 16
     return __builtin_amdgcn_perm(static_cast<uint32_t>(ws), static_cast<uint32_t>(wc), 0x05040100u);
   };
-  if constexpr (Mode == 2) {
-    for (int j = 0; j < nrun; ++j) put(j, static_cast<uint32_t>(j));
-    return;
-  }
   unsigned long long fix = 0;  // wave-uniform: bit j set when some lane left channel c0 + j undecided (nrun <= 64)
-  uint32_t acc = 0;
   constexpr double kMagic = 0x1.8p52;
   // a lane beyond the guard's range: every channel of the wave is evaluated exactly after the walk
   if (__builtin_amdgcn_ballot_w64(!in_range)) fix = nrun >= 64 ? ~0ull : (1ull << nrun) - 1;
-  auto emit = [&](int j, uint32_t word) {  // store (or, diagnostics, fold) the word; step the recurrence
-    if constexpr (Mode == 1)
-      acc += word;
-    else
-      put(j, word);
+  auto emit = [&](int j, uint32_t word) {  // store the word; step the recurrence
+    put(j, word);
     const double r2 = fma(re, cd, -im * sd);
     im = fma(re, sd, im * cd);
     re = r2;
@@ -186,10 +175,6 @@ __global__ __launch_bounds__(256) void q14_table_kernel(Q14TableArgs P) {
       }
       emit(j, pack(wc, ws));
     }
-  }
-  if constexpr (Mode == 1) {
-    if (acc == 0x9e3779b9u) *o = acc;
-    return;
   }
   while (fix) {  // (each lane rewrites its own word: program order makes the exact value the final one)
     const int j = __builtin_ctzll(fix);

@@ -26,9 +26,9 @@ __device__ __forceinline__ int w8_step_base(int s, int A) { return min(32 * s, A
 __host__ __device__ inline int w8_padded_steps(int A) { return 2 * ((((A + 31) >> 5) + 1) / 2); }
 
 // ---- 32-beam slabs (the default integer wide kernel) -------------------------------------------------------------
-// The 16-beam kernel above re-reads each item's voltages once per slab (4x at 64 beams) with a prefetch distance of
-// one step: tools/diag_fused.py showed it latency-bound on those re-reads (no-coef, no-MFMA 442 us against a 164 us
-// read of the same bytes in the same item-major order).  Here a workgroup slab is 32 beams (the Q14 table is 64 KiB:
+// The round-1 16-beam kernel re-read each item's voltages once per slab (4x at 64 beams) with a prefetch distance of
+// one step and was latency-bound on those re-reads (without coefficients and MFMAs 442 us against a 164 us read of
+// the same bytes in the same item-major order).  Here a workgroup slab is 32 beams (the Q14 table is 64 KiB:
 // two workgroups per CU) and a wave 32 samples x 32 beams: half the voltage bytes per MFMA (each lane loads
 // 8-byte runs = 2 samples of 8 antennas), four step buffers of 16 registers (three steps in flight while one is
 // contracted), and the prefetch runs on across the wave's chunks so the next chunk's steps load under the stores.
@@ -80,50 +80,23 @@ __device__ __forceinline__ void w32_expand_unit(int8_t* lb, int ml, int g, const
 // ~28 VALU of 64-bit address arithmetic per step, but their SGPRs pushed this 247-VGPR kernel into spills.)
 // (kept as 8-byte vectors: split into scalar arrays, the pairs were re-packed into the loop's registers with copies
 // that made the prologue wait for its own prefetch)
-template <int Mode>
 __device__ __forceinline__ void w32_load(const uint8_t* __restrict__ base, size_t ant_stride, uint32_t loff, int s,
                                          int A, u32x2_t (&d)[8]) {
   const int a0 = w8_step_base(s, A);
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    if constexpr (Mode & 8) {
-      d[q] = u32x2_t{loff * 0x01010101u + s + q, loff * 0x01010101u + s - q};
-      continue;
-    }
+  for (int q = 0; q < 8; ++q)
     d[q] = *reinterpret_cast<const u32x2_t*>(base + static_cast<size_t>(a0 + q) * ant_stride + loff);
-  }
 }
 
 // The same loads through a buffer resource on the workgroup's (b, c0) block: every load is buffer_load_dwordx2 with
 // the lane part of the offset in one VGPR (antenna group 8h of the step, the sample pair) and the wave-uniform part
 // -- row (a0 + q) of the step, the channel -- in an SGPR soffset: no per-load 64-bit address arithmetic on the VALU
 // (the pointer form spends a v_mad_u64_u32 and moves per load).  Offsets below 2^31 (the host checks A C T 4).
-template <int Mode>
 __device__ __forceinline__ void w32_load_buf(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t sbase, uint32_t stride,
                                              u32x2_t (&d)[8]) {
-  if constexpr ((Mode & 256) != 0) {
-    // diagnostics (timing only, wrong beams): the same bytes in half the instructions -- lane pair (tl, tl ^ 1) loads
-    // 16 bytes of row 2q + (tl & 1) at the pair's sample offset, without the swap that would hand each lane its own
-    // rows back: is the TA's address rate (8-byte lane loads) what bounds the kernel?
-    const uint32_t odd = (voff >> 3) & 1;  // tl & 1 (voff = hoff + 8 tl)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const u32x4_t v = __builtin_bit_cast(
-          u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff - 8 * odd + odd * stride, sbase + 2 * q * stride, 0));
-      d[2 * q] = u32x2_t{v[0], v[1]};
-      d[2 * q + 1] = u32x2_t{v[2], v[3]};
-    }
-    return;
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    if constexpr (Mode & 8) {
-      d[q] = u32x2_t{voff * 0x01010101u + sbase + q, voff * 0x01010101u + sbase - q};
-      continue;
-    }
-    // (Mode 128, diagnostics: non-temporal voltage loads)
-    d[q] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, sbase + q * stride, (Mode & 128) ? 2 : 0));
-  }
+  for (int q = 0; q < 8; ++q)
+    d[q] = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, sbase + q * stride, 0));
 }
 
 // The step's B fragments [pol][sample] (one v_perm per dword); the voltage registers are free afterwards.
@@ -148,74 +121,13 @@ __device__ __forceinline__ void w32_frags(const u32x2_t (&d)[8], i32x4_t (&f)[2]
     }
 }
 
-// The step's second B fragments [x_im, ~x_re] per pol and sample: the halved limb image's y_im operand (~x = -x - 1
-// stays in int8 where -x overflows at -128; the bias is sum_a Ws per beam, removed at requantisation).  Per raw dword
-// one xor (the re bytes of both pols; unsigned samples: x - 128 in the im bytes, ~(x - 128) in the re bytes) and per
-// fragment dword one v_perm.
-template <bool Signed = true>
-__device__ __forceinline__ void w32_frags_im(const u32x2_t (&d)[8], i32x4_t (&f)[2][2]) {
-  constexpr uint32_t kFlip = Signed ? 0x00ff00ffu : 0x807f807fu;
-  uint32_t nd[8][2];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    nd[q][0] = d[q].x ^ kFlip;
-    nd[q][1] = d[q].y ^ kFlip;
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      uint32_t w[4];
-#pragma unroll
-      for (int m2 = 0; m2 < 4; ++m2)
-        w[m2] = __builtin_amdgcn_perm(nd[2 * m2 + 1][i], nd[2 * m2][i], p ? 0x06070203u : 0x04050001u);
-      f[p][i] = i32x4_t{static_cast<int>(w[0]), static_cast<int>(w[1]), static_cast<int>(w[2]), static_cast<int>(w[3])};
-    }
-}
-
 // 32 MFMAs of one step: per tile t (16 real columns) the two limbs' A fragments from LDS, 2 pols x 2 samples.
-template <int Mode>
-__device__ __forceinline__ void w32_mfma(const int4* __restrict__ fr, int s, int lane, const i32x4_t (&f0)[2][2],
-                                         i32x4_t (&hi)[2][2][4], i32x4_t (&lo)[2][2][4],
-                                         const i32x4_t (&f1)[2][2] = {}) {
+__device__ __forceinline__ void w32_mfma(const int4* __restrict__ fr, int s, int lane, const i32x4_t (&f)[2][2],
+                                         i32x4_t (&hi)[2][2][4], i32x4_t (&lo)[2][2][4]) {
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    const i32x4_t (&f)[2][2] = (Mode & 16) && t >= 2 ? f1 : f0;  // measurement: tiles 2, 3 on the second fragments
     const int4 x0 = fr[(((s * 4 + t) * 2 + 0) * 64) + lane];
     const int4 x1 = fr[(((s * 4 + t) * 2 + 1) * 64) + lane];
-    const i32x4_t chi = i32x4_t{x0.x, x0.y, x0.z, x0.w}, clo = i32x4_t{x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if constexpr (Mode & 2) {
-          hi[p][i][t] += f[p][i] + chi;
-          lo[p][i][t] += f[p][i] + clo;
-        } else {
-          hi[p][i][t] = mfma_i8(chi, f[p][i], hi[p][i][t]);
-          lo[p][i][t] = mfma_i8(clo, f[p][i], lo[p][i][t]);
-        }
-      }
-  }
-}
-
-// The same 32 MFMAs with the next tile's two A fragments read from LDS while the current tile's MFMAs issue (two
-// register sets): the single-set form made the compiler issue each tile's reads one MFMA before their use, so every
-// step waited out the LDS latency four times (ISA: s_waitcnt lgkmcnt(1) between the MFMAs of consecutive tiles).
-template <int Mode>
-__device__ __forceinline__ void w32_mfma_pf(const int4* __restrict__ fr, int s, int lane, const i32x4_t (&f)[2][2],
-                                            i32x4_t (&hi)[2][2][4], i32x4_t (&lo)[2][2][4]) {
-  int4 a[2][2];  // [register set][limb]
-  a[0][0] = fr[((s * 4 + 0) * 2 + 0) * 64 + lane];
-  a[0][1] = fr[((s * 4 + 0) * 2 + 1) * 64 + lane];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (t + 1 < 4) {
-      a[(t + 1) & 1][0] = fr[((s * 4 + t + 1) * 2 + 0) * 64 + lane];
-      a[(t + 1) & 1][1] = fr[((s * 4 + t + 1) * 2 + 1) * 64 + lane];
-    }
-    __builtin_amdgcn_sched_barrier(0);  // (else the scheduler sinks the reads back to one MFMA before their use)
-    const int4 x0 = a[t & 1][0], x1 = a[t & 1][1];
     const i32x4_t chi = i32x4_t{x0.x, x0.y, x0.z, x0.w}, clo = i32x4_t{x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
     for (int p = 0; p < 2; ++p)
@@ -224,20 +136,12 @@ __device__ __forceinline__ void w32_mfma_pf(const int4* __restrict__ fr, int s, 
         hi[p][i][t] = mfma_i8(chi, f[p][i], hi[p][i][t]);
         lo[p][i][t] = mfma_i8(clo, f[p][i], lo[p][i][t]);
       }
-    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// Mode (diagnostics only): 1 synthetic coefficients, 2 no MFMA, 4 no stores, 8 no voltage loads, 64 model loads
-// without the phasor math, 256 the phasor math on register-made delays (no model loads).
-template <bool Signed, int Mode = 0, bool Gain = false>
+template <bool Signed, bool Gain = false>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(FusedArgs P) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) int4 lds4[];
-  // Mode 128 (diagnostics): per-wave s_memtime cycles of the phases -> P.gain as uint64 [wave][4]: coefficient
-  // phase (to the barrier), contraction loops, requantise + stores, total
-  unsigned long long st_t0 = 0, st_c = 0, st_l = 0, st_s = 0, st_m = 0;
-  if constexpr ((Mode & 128) != 0) st_t0 = __builtin_amdgcn_s_memtime();
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
   int slab, bc;
@@ -269,7 +173,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
   // (past the wave's last step it repeats that step: the same, just-fetched bytes, and straight-line code)
   auto issue = [&](u32x2_t (&d)[8]) {
     const uint32_t loff = hoff + static_cast<uint32_t>(min(lchunk * 16 + tl, T2 - 1)) * 8u;
-    w32_load<Mode>(base, ant_stride, loff, ls, P.A, d);
+    w32_load(base, ant_stride, loff, ls, P.A, d);
     // advance with selects, not branches: a branch here made the compiler re-home the step buffers through copies
     // (and wait for their loads) at the merge
     ++issued;
@@ -296,12 +200,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
     for (int j = 0; j < kBatch; ++j) {
       const int sa = sa0 + 8 * (j0 + j), st = sa >> 5;
       const int a = min(w8_step_base(st, P.A) + (sa & 31), P.A - 1);
-      if constexpr ((Mode & 256) != 0) {  // diagnostics: no model loads, register-made delays (same math after)
-        const float u = static_cast<float>(a * 37 + ml * 11 + j0);
-        dv[j] = float4{u * 1e-10f, 0.0f, u * 1e-3f - 3.0f, 0.0f};
-        gv[j] = 1.0f;
-        continue;
-      }
       dv[j] = dv_row[a];
       if constexpr (Gain)
         gv[j] = g_row[a];
@@ -311,7 +209,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
   };
   float4 dv_first[kBatch];
   float gv_first[kBatch];
-  if constexpr (!(Mode & 1)) batch_model(0, dv_first, gv_first);
+  batch_model(0, dv_first, gv_first);
   __builtin_amdgcn_sched_barrier(0);
 
   u32x2_t d0[8], d1[8], d2[8], d3[8];
@@ -328,8 +226,8 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
     int cs0 = 0, cs1 = 0;
     const int off0 = coef8_byte(2 * sa0, 2 * ml, 4, 0);
     // the model batches are software-pipelined: batch j0 + kBatch is requested before batch j0's phasors, so each
-    // batch's (L2) load latency hides under the previous batch's float64 work -- measured per wave (s_memtime,
-    // diagnostics Mode 128), four load-then-compute batches were 40 % of a wave's lifetime
+    // batch's (L2) load latency hides under the previous batch's float64 work -- measured per wave (s_memtime
+    // stamps of the phases), four load-then-compute batches were 40 % of a wave's lifetime
     float4 dv[kBatch];
     float gv[kBatch];
 #pragma unroll
@@ -340,7 +238,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
     for (int j0 = 0; j0 < nj; j0 += kBatch) {
       float4 dvn[kBatch];
       float gvn[kBatch];
-      if constexpr (!(Mode & 1)) batch_model(j0 + kBatch, dvn, gvn);  // clamped: past the end it rereads the row
+      batch_model(j0 + kBatch, dvn, gvn);  // clamped: past the end it rereads the row
       bool valid[kBatch];
       int wc[kBatch], ws[kBatch];
 #pragma unroll
@@ -349,21 +247,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
         const int a = w8_step_base(st, P.A) + (sa & 31);
         valid[j] = j0 + j < nj && m_ok && a >= 32 * st;  // rows an earlier step already covered stay zero
       }
-      if constexpr (Mode & 1) {
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-          wc[j] = valid[j] ? 8192 + 16 * j + tid : 0;
-          ws[j] = valid[j] ? 4096 - 16 * j : 0;
-        }
-      } else if constexpr ((Mode & 64) != 0) {  // diagnostics: model loads kept, a few VALU instead of the phasors
-#pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-          wc[j] = valid[j] ? (static_cast<int>(dv[j].x * 1e12f + dv[j].y) & 8191) : 0;
-          ws[j] = valid[j] ? (static_cast<int>(dv[j].z * 1e3f + dv[j].w) & 8191) : 0;
-        }
-      } else {
-        q14_coeffs<kBatch, true, false, true>(dv, gv, valid, ch, P.ctot, P.ts, P.k, dt, P.gain, wc, ws);
-      }
+      q14_coeffs<kBatch, true>(dv, gv, valid, ch, P.ctot, P.ts, P.k, dt, P.gain, wc, ws);
 #pragma unroll
       for (int j = 0; j < kBatch; ++j) {
         if (j0 + j >= nj) break;
@@ -378,12 +262,10 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
         cs0 += Wc - Ws;
         cs1 += Ws + Wc;
       }
-      if constexpr (!(Mode & 1)) {
 #pragma unroll
-        for (int j = 0; j < kBatch; ++j) {
-          dv[j] = dvn[j];
-          gv[j] = gvn[j];
-        }
+      for (int j = 0; j < kBatch; ++j) {
+        dv[j] = dvn[j];
+        gv[j] = gvn[j];
       }
     }
     if constexpr (!Signed) {
@@ -398,10 +280,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
     }
   }
   lds_barrier();  // the table is complete; the voltage prefetch stays in flight
-  if constexpr ((Mode & 128) != 0) {
-    st_m = __builtin_amdgcn_s_memtime();
-    st_c = st_m - st_t0;
-  }
 
   const float s32 = P.out_scale * 0x1p-14f;
   const int M2 = 2 * P.M;
@@ -417,102 +295,67 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
 #pragma unroll
         for (int t = 0; t < 4; ++t) hi[p][i][t] = lo[p][i][t] = i32x4_t{0, 0, 0, 0};
     // four steps in flight; a step's buffer is reloaded as soon as its fragments are built
-    if constexpr ((Mode & 128) != 0) st_m = __builtin_amdgcn_s_memtime();
     for (int s = 0; s < Sp; s += 4) {
       i32x4_t f[2][2];
       w32_frags<Signed>(d0, f);
       issue(d0);
-      w32_mfma<Mode>(lds4, s, lane, f, hi, lo);
+      w32_mfma(lds4, s, lane, f, hi, lo);
       w32_frags<Signed>(d1, f);
       issue(d1);
-      w32_mfma<Mode>(lds4, s + 1, lane, f, hi, lo);
+      w32_mfma(lds4, s + 1, lane, f, hi, lo);
       w32_frags<Signed>(d2, f);
       issue(d2);
-      w32_mfma<Mode>(lds4, s + 2, lane, f, hi, lo);
+      w32_mfma(lds4, s + 2, lane, f, hi, lo);
       w32_frags<Signed>(d3, f);
       issue(d3);
-      w32_mfma<Mode>(lds4, s + 3, lane, f, hi, lo);
+      w32_mfma(lds4, s + 3, lane, f, hi, lo);
     }
-    if constexpr ((Mode & 128) != 0) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      st_l += t - st_m;
-      st_m = t;
-    }
-    if constexpr (Mode & 4) {
-      int sum = 0;
 #pragma unroll
-      for (int p = 0; p < 2; ++p)
+    for (int p = 0; p < 2; ++p) {
+      uint32_t pk[2][4];  // [sample i][tile t] -> 4 packed int8 columns 16 t + 4 h + r
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int t = 0; t < 4; ++t) sum += hi[p][i][t][0] ^ lo[p][i][t][3];
-      if (sum == 0x12345678) reinterpret_cast<int*>(P.y)[tid] = sum;
-    } else {
+        for (int t = 0; t < 4; ++t) {
+          uint32_t qb[4];
 #pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        uint32_t pk[2][4];  // [sample i][tile t] -> 4 packed int8 columns 16 t + 4 h + r
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            uint32_t qb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int y = (hi[p][i][t][r] << 8) + lo[p][i][t][r];
-              if constexpr (!Signed) {  // unsigned samples: 128 * the column sum (wave partials)
-                const int cl = 16 * t + 4 * h + r;
-                y += 128 * (partial[(cl >> 5) * 32 + (cl & 31)] + partial[((cl >> 5) + 2) * 32 + (cl & 31)]);
-              }
-              qb[r] = requant_bits(y, s32);
+          for (int r = 0; r < 4; ++r) {
+            int y = (hi[p][i][t][r] << 8) + lo[p][i][t][r];
+            if constexpr (!Signed) {  // unsigned samples: 128 * the column sum (wave partials)
+              const int cl = 16 * t + 4 * h + r;
+              y += 128 * (partial[(cl >> 5) * 32 + (cl & 31)] + partial[((cl >> 5) + 2) * 32 + (cl & 31)]);
             }
-            pk[i][t] = pack_low_bytes(qb[0], qb[1], qb[2], qb[3]);
+            qb[r] = requant_bits(y, s32);
           }
-        const size_t prow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T);
-        if (full) {
-          // 4x4 transpose over (h, t): lane (tl, h) gets columns 16 h .. 16 h + 15 of sample 2 tq + i
+          pk[i][t] = pack_low_bytes(qb[0], qb[1], qb[2], qb[3]);
+        }
+      const size_t prow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T);
+      if (full) {
+        // 4x4 transpose over (h, t): lane (tl, h) gets columns 16 h .. 16 h + 15 of sample 2 tq + i
 #pragma unroll
-          for (int i = 0; i < 2; ++i) transpose_rows4(pk[i]);
-          if (tq < T2) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq + i) * M2 + 2 * m0 + 16 * h;
-              if constexpr ((Mode & 16) != 0)  // diagnostics: non-temporal stores
-                __builtin_nontemporal_store(u32x4_t{pk[i][0], pk[i][1], pk[i][2], pk[i][3]},
-                                            reinterpret_cast<u32x4_t*>(o));
-              else
-                *reinterpret_cast<u32x4_t*>(o) = u32x4_t{pk[i][0], pk[i][1], pk[i][2], pk[i][3]};
-            }
-          }
-        } else if (tq < T2) {  // partial slab / unaligned rows: byte stores with the beam guard
+        for (int i = 0; i < 2; ++i) transpose_rows4(pk[i]);
+        if (tq < T2) {
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq + i) * M2 + 2 * m0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int col = 16 * t + 4 * h + r;
-                if (2 * m0 + col < M2) o[col] = static_cast<int8_t>((pk[i][t] >> (8 * r)) & 255);
-              }
+            int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq + i) * M2 + 2 * m0 + 16 * h;
+            *reinterpret_cast<u32x4_t*>(o) = u32x4_t{pk[i][0], pk[i][1], pk[i][2], pk[i][3]};
           }
+        }
+      } else if (tq < T2) {  // partial slab / unaligned rows: byte stores with the beam guard
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq + i) * M2 + 2 * m0;
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int col = 16 * t + 4 * h + r;
+              if (2 * m0 + col < M2) o[col] = static_cast<int8_t>((pk[i][t] >> (8 * r)) & 255);
+            }
         }
       }
     }
-    if constexpr ((Mode & 128) != 0) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      st_s += t - st_m;
-    }
     chunk += 4;
-  }
-  if constexpr ((Mode & 128) != 0) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(const_cast<float*>(P.gain)) +
-                            (static_cast<size_t>(blockIdx.x) * 4 + wave) * 4;
-    if (lane == 0) {
-      o[0] = st_c;
-      o[1] = st_l;
-      o[2] = st_s;
-      o[3] = __builtin_amdgcn_s_memtime() - st_t0;
-    }
   }
 }
 
@@ -525,7 +368,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
 // from one channel into the next, so only a workgroup's first channel starts cold (measured on the one-channel form: a cold start -- table +
 // first voltage steps -- per (channel, slab) cost ~50 us of 430 at config 4 in a round-3 ablation whose record was
 // not kept).
-// Mode (diagnostics): 1 no table loads / expansion, 4 no stores, 8 no voltage loads.
 constexpr int kW32TChannels = 4;
 
 // Early: request the next channel's table during the last pass's pol-1 stores (else after the last pass).
@@ -535,10 +377,9 @@ constexpr int kW32TChannels = 4;
 // every four steps in the runtime-bounded form.
 // BufLd: voltage loads through a buffer resource (w32_load_buf).  Pow2: the output scale is a power of two, so the
 // requantisation's multiply and magic add fuse into one exact FMA (requant_bits<true>).
-template <bool Signed, int Mode = 0, bool Early = true, int kSp = 0, int kNP = 0, int kNB = 4, int kCh = kW32TChannels,
+template <bool Signed, bool Early = true, int kSp = 0, int kNP = 0, int kNB = 4, int kCh = kW32TChannels,
           bool BufLd = false, bool Pow2 = false>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(FusedArgs P) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   extern __shared__ __attribute__((aligned(16))) int4 lds4[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 4, tl = lane & 15;
@@ -582,11 +423,11 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
       const uint32_t voff = hoff + static_cast<uint32_t>(min((wave + 4 * lp) * 16 + tl, T2 - 1)) * 8u;
       const uint32_t sbase = static_cast<uint32_t>(w8_step_base(ls, P.A)) * static_cast<uint32_t>(ant_stride) +
                              static_cast<uint32_t>(lk) * ch_bytes;
-      w32_load_buf<Mode>(vrs, voff, sbase, static_cast<uint32_t>(ant_stride), d);
+      w32_load_buf(vrs, voff, sbase, static_cast<uint32_t>(ant_stride), d);
     } else {
       const uint32_t loff = hoff + static_cast<uint32_t>(lk) * ch_bytes +
                             static_cast<uint32_t>(min((wave + 4 * lp) * 16 + tl, T2 - 1)) * 8u;
-      w32_load<Mode>(base, ant_stride, loff, ls, P.A, d);
+      w32_load(base, ant_stride, loff, ls, P.A, d);
     }
     ++issued;  // selects, not branches (see the one-channel kernel); past the last step it repeats that step
     const bool adv = issued < total;
@@ -597,19 +438,16 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
   };
   u32x4_t tq[4][2];  // this thread's table units of the channel being staged
   auto load_table = [&](int kc) {
-    if constexpr ((Mode & 1) == 0) {
-      // a buffer resource on the channel's (uniform) table block + 32-bit lane offsets: no 64-bit per-lane pointers
-      // (hoisted out of the channel loop they were spilled)
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<u32x4_t*>(tbase + static_cast<size_t>(kc) * tstride), 0, 0x7fffffff, 0x00020000);
+    // a buffer resource on the channel's (uniform) table block + 32-bit lane offsets: no 64-bit per-lane pointers
+    // (hoisted out of the channel loop they were spilled)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<u32x4_t*>(tbase + static_cast<size_t>(kc) * tstride), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)  // Sp / 2 units (4 or 2); unconditional loads (clamped unit)
+    for (int j = 0; j < 4; ++j)  // Sp / 2 units (4 or 2); unconditional loads (clamped unit)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-          tq[j][hf] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                                      rs, static_cast<uint32_t>(((min(j, Sp / 2 - 1) * 2 + hf) * 256 + tid) * 16), 0,
-                                                      (Mode & 64) ? 2 : 0));  // (Mode 64, diagnostics: non-temporal)
-    }
+      for (int hf = 0; hf < 2; ++hf)
+        tq[j][hf] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                                    rs, static_cast<uint32_t>(((min(j, Sp / 2 - 1) * 2 + hf) * 256 + tid) * 16), 0, 0));
   };
   load_table(0);
   __builtin_amdgcn_sched_barrier(0);
@@ -624,7 +462,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
   const bool full = m0 + kW32Beams <= P.M && (M2 & 15) == 0;  // 16-byte row pieces (uniform)
   for (int kc = 0; kc < nk; ++kc) {
     const int c = c0 + kc;
-    if constexpr ((Mode & 1) == 0) {  // the channel's table -> LDS limb image (+ unsigned column sums)
+    {  // the channel's table -> LDS limb image (+ unsigned column sums)
       const int ml = tid & 31;
       int cs0 = 0, cs1 = 0;
 #pragma unroll
@@ -673,18 +511,12 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
         // step's refill after its fragments
 #pragma unroll
         for (int s = 0; s < kSp; ++s) {
-          constexpr int dummy = 0;
-          (void)dummy;
-          i32x4_t f[2][2], fi[2][2];
+          i32x4_t f[2][2];
           const int j = (pass * kSp + s) % NB;
           w32_frags<Signed>(db[j], f);
-          if constexpr ((Mode & 16) != 0) w32_frags_im(db[j], fi);
           __builtin_amdgcn_sched_barrier(0);
           issue(db[j]);
-          if constexpr ((Mode & 32) != 0)
-            w32_mfma_pf<0>(lds4, s, lane, f, hi, lo);
-          else
-            w32_mfma<Mode & 16>(lds4, s, lane, f, hi, lo, fi);
+          w32_mfma(lds4, s, lane, f, hi, lo);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -696,74 +528,62 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
           for (int j = 0; j < 2; ++j) {
             w32_frags<Signed>(db[j], f);
             issue(db[j]);
-            w32_mfma<0>(lds4, s + j, lane, f, hi, lo);
+            w32_mfma(lds4, s + j, lane, f, hi, lo);
           }
         }
       }
       // unconditional in the last pass (the workgroup's last channel re-reads its own table, from L2): with a
       // conditional request the previous table's registers stayed live through every pass (phi at the back-edge)
       constexpr bool next_table = kLast && Early;
-      if constexpr (Mode & 4) {
-        if constexpr (next_table) load_table(min(kc + 1, nk - 1));
-        int sum = 0;
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
+      for (int p = 0; p < 2; ++p) {
+        // the next channel's table, requested once pol 0's accumulators are dead (registers) -- its latency runs
+        // under pol 1's stores and the barrier
+        if constexpr (next_table)
+          if (p == 1) {  // pinned: scheduled earlier, the loads overlapped pol 0's accumulators (spills)
+            __builtin_amdgcn_sched_barrier(0);
+            load_table(min(kc + 1, nk - 1));
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        uint32_t pk[2][4];  // [sample i][tile t] -> 4 packed int8 columns 16 t + 4 h + r
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) sum += hi[p][i][t][0] ^ lo[p][i][t][3];
-        if (sum == 0x12345678) reinterpret_cast<int*>(P.y)[tid] = sum;
-      } else {
+          for (int t = 0; t < 4; ++t) {
+            uint32_t qb[4];
+            int4 cs = int4{0, 0, 0, 0};  // unsigned: the 4 columns' sums, one 16-byte LDS read
+            if constexpr (!Signed) cs = reinterpret_cast<const int4*>(partial)[4 * t + h];
+            const int csr[4] = {cs.x, cs.y, cs.z, cs.w};
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          // the next channel's table, requested once pol 0's accumulators are dead (registers) -- its latency runs
-          // under pol 1's stores and the barrier
-          if constexpr (next_table)
-            if (p == 1) {  // pinned: scheduled earlier, the loads overlapped pol 0's accumulators (spills)
-              __builtin_amdgcn_sched_barrier(0);
-              load_table(min(kc + 1, nk - 1));
-              __builtin_amdgcn_sched_barrier(0);
+            for (int r = 0; r < 4; ++r) {
+              int y = (hi[p][i][t][r] << 8) + lo[p][i][t][r];
+              if constexpr (!Signed) y += 128 * csr[r];
+              qb[r] = requant_bits<Pow2>(y, s32);
             }
-          uint32_t pk[2][4];  // [sample i][tile t] -> 4 packed int8 columns 16 t + 4 h + r
+            pk[i][t] = pack_low_bytes(qb[0], qb[1], qb[2], qb[3]);
+          }
+        const size_t prow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T);
+        if (full) {
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-              uint32_t qb[4];
-              int4 cs = int4{0, 0, 0, 0};  // unsigned: the 4 columns' sums, one 16-byte LDS read
-              if constexpr (!Signed) cs = reinterpret_cast<const int4*>(partial)[4 * t + h];
-              const int csr[4] = {cs.x, cs.y, cs.z, cs.w};
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                int y = (hi[p][i][t][r] << 8) + lo[p][i][t][r];
-                if constexpr (!Signed) y += 128 * csr[r];
-                qb[r] = requant_bits<Pow2>(y, s32);
-              }
-              pk[i][t] = pack_low_bytes(qb[0], qb[1], qb[2], qb[3]);
-            }
-          const size_t prow = ((static_cast<size_t>(b) * 2 + p) * P.C + c) * static_cast<size_t>(P.T);
-          if (full) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) transpose_rows4(pk[i]);
-            if (tq2 < T2) {
-#pragma unroll
-              for (int i = 0; i < 2; ++i) {
-                int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq2 + i) * M2 + 2 * m0 + 16 * h;
-                *reinterpret_cast<u32x4_t*>(o) = u32x4_t{pk[i][0], pk[i][1], pk[i][2], pk[i][3]};
-              }
-            }
-          } else if (tq2 < T2) {  // partial slab / unaligned rows: byte stores with the beam guard
+          for (int i = 0; i < 2; ++i) transpose_rows4(pk[i]);
+          if (tq2 < T2) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-              int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq2 + i) * M2 + 2 * m0;
-#pragma unroll
-              for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                  const int col = 16 * t + 4 * h + r;
-                  if (2 * m0 + col < M2) o[col] = static_cast<int8_t>((pk[i][t] >> (8 * r)) & 255);
-                }
+              int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq2 + i) * M2 + 2 * m0 + 16 * h;
+              *reinterpret_cast<u32x4_t*>(o) = u32x4_t{pk[i][0], pk[i][1], pk[i][2], pk[i][3]};
             }
+          }
+        } else if (tq2 < T2) {  // partial slab / unaligned rows: byte stores with the beam guard
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            int8_t* o = reinterpret_cast<int8_t*>(P.y) + (prow + 2 * tq2 + i) * M2 + 2 * m0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int col = 16 * t + 4 * h + r;
+                if (2 * m0 + col < M2) o[col] = static_cast<int8_t>((pk[i][t] >> (8 * r)) & 255);
+              }
           }
         }
       }
@@ -862,17 +682,8 @@ __device__ __forceinline__ i32x4_t w32r_frag_im(const i32x4_t& f) {
   return r;
 }
 
-// Mode (diagnostics only): 4 no stores, 8 no voltage DMA (the slots' stale bytes), 16 no table loads / expansion,
-// 32 the step's four DMA pieces issued as one burst before its MFMAs (the product spreads them, one per 8 MFMAs),
-// 64 a pass's four beam stores back to back after its requantisation; 128 the DMA pieces issued through a
-// zero-record descriptor (the instructions and waits stay, no bytes move: their issue cost alone), 256 the same for
-// the beam stores; 512 the four pieces of a step at one M0 (the LDS offset in the instruction's immediate, the
-// global offset compensated in soffset); 1024 every channel's voltages from the workgroup's first channel (L2
-// hits after the first), 2048 every beam store into one of 256 8 KiB blocks (L2-resident writes), 4096 the second
-// slab's voltage DMA through a zero-record descriptor (one slab's bytes through the CU path: wrong beams for it).
-template <bool Pow2, int Mode = 0>
+template <bool Pow2>
 __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(FusedArgs P) {
-  static_assert(Mode == 0, "diagnostic Mode bits in a product instantiation");
   constexpr int Sp = 8, NP = 2, kCh = kW32RChannels;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -895,8 +706,8 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   const uint32_t ant_stride = static_cast<uint32_t>(C) * static_cast<uint32_t>(P.T) * 4u;  // host: A C T 4 < 2^31
   const uint32_t ch_bytes = static_cast<uint32_t>(P.T) * 4u;
   const uint8_t* base = P.raw + (static_cast<size_t>(b) * P.A * C + c0) * static_cast<size_t>(P.T) * 4;
-  const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(base), 0, ((Mode & 128) || ((Mode & 4096) && slab == 1)) ? 0 : 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, 0x7fffffff,
+                                                                        0x00020000);
   const uint32_t dma_voff = static_cast<uint32_t>(8 * ((lane >> 3) & 3) + (lane >> 5)) * ant_stride +
                             16u * static_cast<uint32_t>(lane & 7);
   int4* const slot0 = w32r_slot0 + 256 * wave;
@@ -909,23 +720,12 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   auto dma_sb = [&]() {
     // (readfirstlane: a loop-carried part of it landed in a VGPR, and the DMA's soffset then became a waterfall loop)
     return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(w8_step_base(ls, P.A)) * ant_stride +
-                                          static_cast<uint32_t>((Mode & 1024) ? 0 : lk) * ch_bytes +
+                                          static_cast<uint32_t>(lk) * ch_bytes +
                                           static_cast<uint32_t>(wave + 4 * lp) * 128u);
   };
   auto dma_piece = [&](int4* slot, int k, uint32_t sb) {
-    if constexpr ((Mode & 8) == 0) {
-      if constexpr ((Mode & 512) != 0) {
-        const uint32_t so = sb + 2u * static_cast<uint32_t>(k) * ant_stride - 1024u * k;
-        switch (k) {  // (the immediate must be a constant: k is one after unrolling)
-#define BF_W32R_DMA(K) \
-  case K: __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void_ptr)slot, 16, dma_voff, so, 1024 * K, 0); break;
-          BF_W32R_DMA(0) BF_W32R_DMA(1) BF_W32R_DMA(2) BF_W32R_DMA(3)
-#undef BF_W32R_DMA
-        }
-      } else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void_ptr)(slot + 64 * k), 16, dma_voff,
-                                                 sb + 2u * static_cast<uint32_t>(k) * ant_stride, 0, 0);
-    }
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(vrs, (lds_void_ptr)(slot + 64 * k), 16, dma_voff,
+                                             sb + 2u * static_cast<uint32_t>(k) * ant_stride, 0, 0);
   };
   auto advance = [&]() {
     ++issued;
@@ -954,33 +754,29 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   const size_t tstride = static_cast<size_t>(P.nslabs) * 256 * Sp;  // u32x4 per channel
   u32x4_t tq[4][2];
   auto load_table = [&](int kc) {
-    if constexpr ((Mode & 16) == 0) {
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<u32x4_t*>(tbase + static_cast<size_t>(kc) * tstride), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<u32x4_t*>(tbase + static_cast<size_t>(kc) * tstride), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
-          tq[j][hf] = __builtin_bit_cast(
-              u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, static_cast<uint32_t>(((j * 2 + hf) * 256 + tid) * 16), 0, 0));
-    }
+      for (int hf = 0; hf < 2; ++hf)
+        tq[j][hf] = __builtin_bit_cast(
+            u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, static_cast<uint32_t>(((j * 2 + hf) * 256 + tid) * 16), 0, 0));
   };
   // the image of the staged channel + this wave's partial sum_a Ws per beam (lanes ml and ml + 32 hold the same beam)
   auto expand = [&]() {
-    if constexpr ((Mode & 16) == 0) {
-      const int ml = tid & 31;
-      int ws = 0;
+    const int ml = tid & 31;
+    int ws = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w32r_expand_unit(w32r_img, ml, (tid >> 5) + 8 * j, tq[j][0], tq[j][1]);
+    for (int j = 0; j < 4; ++j) {
+      w32r_expand_unit(w32r_img, ml, (tid >> 5) + 8 * j, tq[j][0], tq[j][1]);
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf)
+      for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) ws += static_cast<int>(tq[j][hf][q]) >> 16;
-      }
-      ws += __shfl_xor(ws, 32);
-      if (lane < 32) w32r_ws[32 * wave + ml] = ws;
+        for (int q = 0; q < 4; ++q) ws += static_cast<int>(tq[j][hf][q]) >> 16;
     }
+    ws += __shfl_xor(ws, 32);
+    if (lane < 32) w32r_ws[32 * wave + ml] = ws;
   };
 
   load_table(0);
@@ -993,8 +789,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
 
   const float s32 = P.out_scale * 0x1p-14f;
   const int M2 = 2 * P.M;
-  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, (Mode & 256) ? 0 : 0x7fffffff,
-                                                                        0x00020000);
+  const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(P.y, 0, 0x7fffffff, 0x00020000);
   // the lane's part of a beam-row store offset (sample 2 tl + i of the wave's 32, row piece of lane group h)
   const uint32_t so_lane = static_cast<uint32_t>(2 * tl * M2 + 16 * (h >> 1) + 32 * (h & 1));
   for (int kc = 0; kc < nk; ++kc) {
@@ -1024,10 +819,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
         asm volatile("" ::"v"(f[0][0]), "v"(f[0][1]), "v"(f[1][0]), "v"(f[1][1]) : "memory");
         __builtin_amdgcn_sched_barrier(0);
         const uint32_t sb = dma_sb();
-        if constexpr ((Mode & 32) != 0) {  // (diagnostics: the four pieces as one burst -- 370.0 vs 362.7 us spread)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) dma_piece(slot, k, sb);
-        }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int4 x0 = w32r_img[((s * 2 + t) * 2 + 0) * 64 + lane];
@@ -1035,11 +826,11 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
           const i32x4_t ahi = i32x4_t{x0.x, x0.y, x0.z, x0.w}, alo = i32x4_t{x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
           for (int p = 0; p < 2; ++p) {
-            if constexpr ((Mode & 32) == 0) {  // one DMA piece per 8 MFMAs, not a burst of 4 (-2 %, r5_ab1)
-              __builtin_amdgcn_sched_barrier(0);
-              dma_piece(slot, 2 * t + p, sb);
-              __builtin_amdgcn_sched_barrier(0);
-            }
+            // one DMA piece per 8 MFMAs, not the four as a burst before the step's MFMAs (-2 %: 362.7 vs 370.0 us,
+            // r5_ab1)
+            __builtin_amdgcn_sched_barrier(0);
+            dma_piece(slot, 2 * t + p, sb);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
               rh[p][i][t] = mfma_i8(ahi, f[p][i], rh[p][i][t]);
@@ -1078,58 +869,32 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
         bias[t][2] = -acc.z;
         bias[t][3] = -acc.w;
       }
-      if constexpr ((Mode & 4) != 0) {
-        int sum = 0;
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
+      for (int p = 0; p < 2; ++p) {
+        const uint32_t prow = static_cast<uint32_t>(((b * 2 + p) * C + c) * P.T);
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i) {
+          uint32_t pk[2][2];  // [tile][dword]
 #pragma unroll
-            for (int t = 0; t < 2; ++t) sum += rh[p][i][t][0] ^ rl[p][i][t][1] ^ ih[p][i][t][2] ^ il[p][i][t][3] ^ bias[t][p];
-        if (sum == 0x12345678) reinterpret_cast<int*>(P.y)[tid] = sum;
-      } else {
-        u32x4_t sd[2][2];  // [pol][sample i]: the 16 store bytes of this lane
-        uint32_t soff[2][2];
+          for (int t = 0; t < 2; ++t) {
+            uint32_t qr[4], qi[4];
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const uint32_t prow = static_cast<uint32_t>(((b * 2 + p) * C + c) * P.T);
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            uint32_t pk[2][2];  // [tile][dword]
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              uint32_t qr[4], qi[4];
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                qr[r] = requant_bits<Pow2>((rh[p][i][t][r] << 8) + rl[p][i][t][r], s32);
-                qi[r] = requant_bits<Pow2>((ih[p][i][t][r] << 8) + il[p][i][t][r] + bias[t][r], s32);
-              }
-              pk[t][0] = pack_low_bytes(qr[0], qi[0], qr[1], qi[1]);
-              pk[t][1] = pack_low_bytes(qr[2], qi[2], qr[3], qi[3]);
+            for (int r = 0; r < 4; ++r) {
+              qr[r] = requant_bits<Pow2>((rh[p][i][t][r] << 8) + rl[p][i][t][r], s32);
+              qi[r] = requant_bits<Pow2>((ih[p][i][t][r] << 8) + il[p][i][t][r] + bias[t][r], s32);
             }
-            const auto sw0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
-            const auto sw1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-            sd[p][i] = u32x4_t{sw0[0], sw1[0], sw0[1], sw1[1]};
-            soff[p][i] = (prow + static_cast<uint32_t>(2 * (wave + 4 * pass) * 16 + i)) * static_cast<uint32_t>(M2) +
-                         static_cast<uint32_t>(2 * m0);
-            if constexpr ((Mode & 2048) != 0) soff[p][i] = static_cast<uint32_t>(blockIdx.x & 255) * 8192u;
-            if constexpr ((Mode & 64) == 0) {
-              __builtin_amdgcn_raw_buffer_store_b128(sd[p][i], yrs, so_lane, soff[p][i], 0);
-              // Two wait states before any VALU may rewrite the store's data VGPRs: hipcc scheduled a write of its
-              // 4th data register right behind this store, and that dword of lanes 12-15 of every row went out
-              // wrong (~1e-5 of the bytes, run to run; tools/diag_w32r.py, tools/store_hazard_check.py).
-              __builtin_amdgcn_sched_barrier(0);
-              asm volatile("s_nop 1");
-              __builtin_amdgcn_sched_barrier(0);
-            }
+            pk[t][0] = pack_low_bytes(qr[0], qi[0], qr[1], qi[1]);
+            pk[t][1] = pack_low_bytes(qr[2], qi[2], qr[3], qi[3]);
           }
-        }
-        if constexpr ((Mode & 64) != 0) {  // (diagnostics: the pass's four stores back to back, one guard)
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) __builtin_amdgcn_raw_buffer_store_b128(sd[p][i], yrs, so_lane, soff[p][i], 0);
+          const auto sw0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
+          const auto sw1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
+          const u32x4_t sd = u32x4_t{sw0[0], sw1[0], sw0[1], sw1[1]};  // the 16 store bytes of this lane
+          const uint32_t soff = (prow + static_cast<uint32_t>(2 * (wave + 4 * pass) * 16 + i)) * static_cast<uint32_t>(M2) +
+                                static_cast<uint32_t>(2 * m0);
+          __builtin_amdgcn_raw_buffer_store_b128(sd, yrs, so_lane, soff, 0);
+          // Two wait states before any VALU may rewrite the store's data VGPRs: hipcc scheduled a write of its
+          // 4th data register right behind this store, and that dword of lanes 12-15 of every row went out
+          // wrong (~1e-5 of the bytes, run to run; tools/store_hazard_check.py).
           __builtin_amdgcn_sched_barrier(0);
           asm volatile("s_nop 1");
           __builtin_amdgcn_sched_barrier(0);
@@ -1147,7 +912,7 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <bool Signed, int Mode>
+template <bool Signed>
 int launch_w32t_contract(FusedArgs P, hipStream_t st);
 
 // The LDS-DMA ring contraction's shape (beamform_fused_i8_w32r_kernel): 8 k-steps, T = 256, whole 32-beam slabs,
@@ -1159,21 +924,18 @@ bool w32r_fits(const FusedArgs& P) {
 }
 
 // The LDS-DMA ring contraction of one launch whose kLayoutW32 table is ready in P.table on `st` (int8 voltages).
-template <int Mode = 0>
+// Pow2: the output scale is a power of two (requant_bits<true>).
+template <bool Pow2>
 int launch_w32r_contract(FusedArgs P, hipStream_t st) {
   const long long groups = static_cast<long long>(P.B) * ((P.C + kW32RChannels - 1) / kW32RChannels);
   const long long grid = P.xcd_order ? (groups + 7) / 8 * 8 * P.nslabs : groups * P.nslabs;
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-  if (scale_is_pow2(P.out_scale * 0x1p-14f))
-    hipLaunchKernelGGL((beamform_fused_i8_w32r_kernel<true, Mode>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kW8Threads), 0, st, P);
-  else
-    hipLaunchKernelGGL((beamform_fused_i8_w32r_kernel<false, Mode>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kW8Threads), 0, st, P);
+  hipLaunchKernelGGL((beamform_fused_i8_w32r_kernel<Pow2>), dim3(static_cast<unsigned>(grid)), dim3(kW8Threads), 0,
+                     st, P);
   BF_LAUNCHED("beamform_fused_i8_w32r_kernel");
 }
 
-template <bool Signed, int Mode = 0>
+template <bool Signed>
 int launch_w32(FusedArgs P, hipStream_t st) {
   const size_t lds = w32_lds_bytes(P.A);
   BF_REQUIRE(lds <= kMaxLds, "bf_beamform_fused: n_ants=%d too large for the integer wide kernel", P.A);
@@ -1186,22 +948,24 @@ int launch_w32(FusedArgs P, hipStream_t st) {
     // the coefficient table of this launch, written by q14_table_kernel just before on `st`
     const int e = launch_q14_table(P, const_cast<uint32_t*>(P.table), kLayoutW32, st);
     if (e != BF_OK) return e;
-    if constexpr (Signed && Mode == 0)
-      if (w32r_fits(P)) return launch_w32r_contract(P, st);  // config 4's shape: the LDS-DMA voltage ring
-    return launch_w32t_contract<Signed, Mode>(P, st);
+    if constexpr (Signed)
+      if (w32r_fits(P))  // config 4's shape: the LDS-DMA voltage ring
+        return scale_is_pow2(P.out_scale * 0x1p-14f) ? launch_w32r_contract<true>(P, st)
+                                                     : launch_w32r_contract<false>(P, st);
+    return launch_w32t_contract<Signed>(P, st);
   }
   if (P.gain)
-    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, Mode, true>), dim3(static_cast<unsigned>(grid)),
+    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, true>), dim3(static_cast<unsigned>(grid)),
                        dim3(kW8Threads), lds, st, P);
   else
-    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, Mode, false>), dim3(static_cast<unsigned>(grid)),
+    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, false>), dim3(static_cast<unsigned>(grid)),
                        dim3(kW8Threads), lds, st, P);
   BF_LAUNCHED("beamform_fused_i8_w32_kernel");
 }
 
 // The table-driven contraction of one launch (or channel chunk: P.c_count, pointers offset by the caller) whose
 // kLayoutW32 table is ready in P.table on `st`.
-template <bool Signed, int Mode>
+template <bool Signed>
 int launch_w32t_contract(FusedArgs P, hipStream_t st) {
   const size_t lds = w32_lds_bytes(P.A);
   {
@@ -1220,16 +984,16 @@ int launch_w32t_contract(FusedArgs P, hipStream_t st) {
     // config 4's shape: the straight-line ring, two step buffers (one step in flight while one is contracted):
     // 377 vs 384 us for three buffers and 403 for the runtime loop (profiles/r3_ab_*, r3_g_*)
     if (straight && buf && pow2)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, Mode, false, 8, 2, 2, 8, true, true>), grid3, block,
+      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 8, 2, 2, 8, true, true>), grid3, block,
                          lds, st, P);
     else if (straight && buf)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, Mode, false, 8, 2, 2, 8, true, false>), grid3, block,
+      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 8, 2, 2, 8, true, false>), grid3, block,
                          lds, st, P);
     else if (buf)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, Mode, false, 0, 0, 4, kW32TChannels, true, false>),
+      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 0, 0, 4, kW32TChannels, true, false>),
                          grid3, block, lds, st, P);
     else  // offsets past 2^31 (A C T 4 >= 2 GiB): the pointer form
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, Mode, false>), grid3, block, lds, st, P);
+      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false>), grid3, block, lds, st, P);
     BF_LAUNCHED("beamform_fused_i8_w32t_kernel");
   }
 }
