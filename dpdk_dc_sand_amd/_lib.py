@@ -84,6 +84,9 @@ PROTOTYPES = {
     "bf_incoherent_beam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                    c_void_p]),
     "bf_incoherent_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_beam_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                               c_void_p]),
+    "bf_detect_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -105,6 +108,8 @@ FUSED_PATH = {"auto": 0, "item": 0x100, "generic": 0x300, "wide": 0x400}
 FUSED_ORDER = {"auto": 0, "channel": 0x1000, "xcd": 0x2000}
 # bf_incoherent_beam flags
 INCOH_SIGNED, INCOH_SUM_POLS = 1, 2
+# bf_beam_detect flags
+DETECT_IN_INT8, DETECT_STOKES_IQUV = 1, 2
 
 
 class BeamformerError(RuntimeError):

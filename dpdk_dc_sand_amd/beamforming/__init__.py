@@ -10,13 +10,16 @@ New (MI355X-native): beamforming.fused -> FusedBeamformerTemplate / FusedBeamfor
 coefficient regeneration + multiply, optional ?beam-weights gains), beamforming.requant -> RequantTemplate /
 Requant, beamforming.streaming -> StreamingBeamformerTemplate / StreamingBeamformer (host -> GPU -> host frames
 with H2D, compute and D2H overlapped), beamforming.incoherent -> IncoherentBeamTemplate / IncoherentBeam (masked
-antenna power sums of the same raw voltages, integrated in time; bit-exact integer contract).
+antenna power sums of the same raw voltages, integrated in time; bit-exact integer contract), beamforming.detect ->
+BeamDetectorTemplate / BeamDetector (Stokes I or IQUV power of the beams, integrated in time and frequency, bound to
+FusedBeamformer.outData).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
 from .beamform_op_sequence import OpSequence, OpSequenceTemplate  # noqa: F401
 from .coeff_generator import CoeffGenerator, CoeffGeneratorTemplate  # noqa: F401
 from .complex_mult_kernel import ComplexMultKernel  # noqa: F401
+from .detect import BeamDetector, BeamDetectorTemplate  # noqa: F401
 from .fused import FusedBeamformer, FusedBeamformerTemplate  # noqa: F401
 from .incoherent import IncoherentBeam, IncoherentBeamTemplate  # noqa: F401
 from .matrix_multiply import MatrixMultiply, MatrixMultiplyTemplate  # noqa: F401

@@ -37,9 +37,10 @@ const char* bf_last_error(void);
  * bf_scatter_plan added (the channel scatter's operation list as a pure host function).  302: ABI 3.2 --
  * bf_beamform_study_single_channel added (the C++ study's fused kernel in its own semantics).  Later 3.2 libraries add
  * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
- * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes. */
+ * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
+ * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes. */
 int bf_abi_version(void);
-/* 1 when this library has the named feature ("incoherent_beam"), 0 for any other name (and for NULL). */
+/* 1 when this library has the named feature ("incoherent_beam", "beam_detect"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -225,6 +226,30 @@ int bf_requant(const float* y, int8_t* q, size_t n, float scale, void* stream);
 int bf_incoherent_beam(const uint8_t* raw, const uint8_t* ant_mask, float* out, int B, int C, int T, int A, int tint,
                        int flags, float scale, void* stream);
 double bf_incoherent_algorithmic_bytes(int B, int C, int T, int A, int tint, int flags, int masked);
+
+/* Beam detector (no reference counterpart): Stokes power of the beams, integrated over windows of `tint` samples and
+ * `fint` channels, straight from the fused operator's output:
+ *   beams : (B, 2, C, T/16, 16, 2M), f32, or int8 with BF_DETECT_IN_INT8 (the BF_FUSED_OUT_INT8 output); the last axis
+ *           is (re, im) per beam, column 2m = re, 2m+1 = im
+ *   out   : f32 (B, S, C/fint, T/tint, M), S = 1 (I), or 4 (I, Q, U, V) with BF_DETECT_STOKES_IQUV
+ * With X = pol 0 and Y = pol 1 of (b, c, t, m):
+ *   I = Xr^2+Xi^2+Yr^2+Yi^2   Q = Xr^2+Xi^2-Yr^2-Yi^2   U = 2(XrYr+XiYi)   V = 2(XiYr-XrYi)   (V = 2 Im(X conj Y))
+ *   acc[b][s][k][j][m] = sum over c in [k*fint, (k+1)*fint), t in [j*tint, (j+1)*tint) of the term s
+ *   out                = float32(float64(acc) * float64(scale))      (one multiply, one round-to-nearest-even)
+ * X = 3+4i, Y = 1+2i gives I, Q, U, V = 30, 20, 22, -4 per sample.  int8 beams (-128 is legal, |term| <= 2^16): acc is
+ * the exact integer sum, so the output is order-independent and bit-exact.  f32 beams: acc is a float64 sum of float64
+ * products of the f32 values (the products are exact); the order of the additions is the kernel's own, fixed, so the
+ * result is deterministic and within N * 2^-53 * (the window's I) of the exact sum, N = 4 * tint * fint, before the
+ * scaling and the float32 rounding.  Every output element is written once (no atomics: `out` need not be zeroed) and
+ * the input is never written.  B, C, T, M >= 1; T % 16 == 0, T <= 2^20; M <= 4096; tint >= 1 divides T; fint >= 1
+ * divides C; tint * fint <= 2^31 (int8 sums stay below 2^53); scale finite and > 0; beams 16-byte, out 4-byte aligned.
+ * bf_detect_algorithmic_bytes: (1 or 4) * B*2*C*T*2M input bytes + 4 * B*S*(C/fint)*(T/tint)*M output bytes; 0 for a
+ * non-positive argument. */
+#define BF_DETECT_IN_INT8 1      /* beams are int8 (the fused operator's BF_FUSED_OUT_INT8 output), else f32 */
+#define BF_DETECT_STOKES_IQUV 2  /* four outputs I, Q, U, V; else I only */
+int bf_beam_detect(const void* beams, float* out, int B, int C, int T, int M, int tint, int fint, int flags,
+                   float scale, void* stream);
+double bf_detect_algorithmic_bytes(int B, int C, int T, int M, int tint, int fint, int flags);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

@@ -5,7 +5,9 @@ stream, random inputs, algorithmic bytes per launch and the achieved fraction of
     python tools/bench_ops.py [--reps 10] [--only cfg3,cfg4]     -> one JSON line per measurement
 At cfg2, cfg3 and cfg4 the incoherent beam follows (integration = T and 16, unmasked), each line with the box's stream
 ceiling for the same read and write bytes (build/libbf_stream.so, `make stream`) measured in the same process;
-`--incoherent` runs only these.
+`--incoherent` runs only these.  The beam detector follows at the same configurations (f32 and int8 beams of the
+configuration's shape, (tint, fint) = (16, 1) and (T, 16), Stokes I and IQUV), each line with the stream ceiling in the
+same way; `--detect` runs only these.
 """
 import argparse
 import ctypes
@@ -20,8 +22,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import accel  # noqa: E402
-from dpdk_dc_sand_amd.beamforming import (CoeffGeneratorTemplate, FusedBeamformerTemplate,  # noqa: E402
-                                          IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
+from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, CoeffGeneratorTemplate,  # noqa: E402
+                                          FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
                                           PreBeamformReorderTemplate)
 
 TS = 1 / 1712e6
@@ -154,25 +156,68 @@ def run_incoherent(ctx, q, name, c, reps, rng):
         del op
 
 
+def run_detect(ctx, q, name, c, reps, rng):
+    """The beam detector over beams of the configuration's shape (random bytes read as int8, Gaussian f32 of rms
+    1000): (tint, fint) = (16, 1) and (T, 16), Stokes I and IQUV, each with the stream ceiling for its own read and
+    write bytes (measured once per distinct byte pair)."""
+    M, C, T, B = c["M"], c["C"], c["T"], c["B"]
+    shape = (B, 2, C, T // 16, 16, 2 * M)
+    ceilings = {}
+    for in_int8 in (False, True):
+        beams = accel.DeviceArray(ctx, shape, np.int8 if in_int8 else np.float32)
+        host = np.empty(shape, beams.dtype)
+        flat = host.reshape(-1)
+        for i in range(0, flat.size, 1 << 24):  # chunked: no whole-cube float64 temporary
+            n = min(1 << 24, flat.size - i)
+            flat[i:i + n] = (rng.integers(-128, 128, n, dtype=np.int8) if in_int8
+                             else 1000 * rng.standard_normal(n, dtype=np.float32))
+        beams.set(q, host)
+        del host, flat
+        for tint, fint in ((16, 1), (T, 16)):
+            for stokes in ("I", "IQUV"):
+                tmpl = BeamDetectorTemplate(ctx, B, C, T, M, time_integration=tint, channel_integration=fint,
+                                            stokes=stokes, in_int8=in_int8)
+                op = tmpl.instantiate(q)
+                op.bind(inBeams=beams)
+                op.ensure_all_bound()
+                t = timeit(q, op, reps)
+                read_bytes, write_bytes = beams.nbytes, op.buffer("outData").nbytes
+                assert tmpl.algorithmic_bytes() == read_bytes + write_bytes
+                if (read_bytes, write_bytes) not in ceilings:
+                    ceilings[read_bytes, write_bytes] = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+                ct, grid, code = ceilings[read_bytes, write_bytes]
+                emit(name, f"detect_{'int8' if in_int8 else 'f32'}_{stokes}_t{tint}_f{fint}", t,
+                     tmpl.algorithmic_bytes(), time_integration=tint, channel_integration=fint, stokes=stokes,
+                     beams="int8" if in_int8 else "f32", read_bytes=read_bytes, write_bytes=write_bytes,
+                     ceiling_us=round(ct * 1e6, 2), ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+                     ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4))
+                del op
+        del beams
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--only", default=",".join(CONFIGS))
     p.add_argument("--fused-only", action="store_true")
     p.add_argument("--incoherent", action="store_true", help="only the incoherent beam and its stream ceiling")
+    p.add_argument("--detect", action="store_true", help="only the beam detector and its stream ceiling")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
     for name in args.only.split(","):
-        if args.incoherent:
-            if name in INCOHERENT_CONFIGS:
+        if args.incoherent or args.detect:
+            if name in INCOHERENT_CONFIGS and args.incoherent:
                 run_incoherent(ctx, q, name, CONFIGS[name], args.reps, rng)
+            if name in INCOHERENT_CONFIGS and args.detect:
+                run_detect(ctx, q, name, CONFIGS[name], args.reps, rng)
             continue
         run_config(ctx, q, name, CONFIGS[name], args.reps, rng, args.fused_only, args.tag)
         if name in INCOHERENT_CONFIGS and not args.fused_only:
             run_incoherent(ctx, q, name, CONFIGS[name], args.reps, rng)
+            run_detect(ctx, q, name, CONFIGS[name], args.reps, rng)
 
 
 if __name__ == "__main__":
