@@ -87,6 +87,9 @@ PROTOTYPES = {
     "bf_beam_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                                c_void_p]),
     "bf_detect_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_voltage_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_float, c_float, c_float, c_void_p]),
+    "bf_vstats_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -110,6 +113,9 @@ FUSED_ORDER = {"auto": 0, "channel": 0x1000, "xcd": 0x2000}
 INCOH_SIGNED, INCOH_SUM_POLS = 1, 2
 # bf_beam_detect flags
 DETECT_IN_INT8, DETECT_STOKES_IQUV = 1, 2
+# bf_voltage_stats flags and the output bit mask of bf_vstats_algorithmic_bytes
+VSTATS_SIGNED = 1
+VSTATS_POWER, VSTATS_SK, VSTATS_FLAGS = 1, 2, 4
 
 
 class BeamformerError(RuntimeError):

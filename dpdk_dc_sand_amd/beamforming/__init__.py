@@ -12,7 +12,8 @@ Requant, beamforming.streaming -> StreamingBeamformerTemplate / StreamingBeamfor
 with H2D, compute and D2H overlapped), beamforming.incoherent -> IncoherentBeamTemplate / IncoherentBeam (masked
 antenna power sums of the same raw voltages, integrated in time; bit-exact integer contract), beamforming.detect ->
 BeamDetectorTemplate / BeamDetector (Stokes I or IQUV power of the beams, integrated in time and frequency, bound to
-FusedBeamformer.outData).
+FusedBeamformer.outData), beamforming.vstats -> VoltageStatsTemplate / VoltageStats (per-antenna power, spectral
+kurtosis and RFI flags of the same raw voltages; antenna_mask_from_flags turns the flags into an antenna mask).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
@@ -26,3 +27,4 @@ from .matrix_multiply import MatrixMultiply, MatrixMultiplyTemplate  # noqa: F40
 from .prebeamform_reorder import PreBeamformReorder, PreBeamformReorderTemplate  # noqa: F401
 from .requant import Requant, RequantTemplate  # noqa: F401
 from .streaming import StreamingBeamformer, StreamingBeamformerTemplate  # noqa: F401
+from .vstats import VoltageStats, VoltageStatsTemplate, antenna_mask_from_flags  # noqa: F401

@@ -38,9 +38,11 @@ const char* bf_last_error(void);
  * bf_beamform_study_single_channel added (the C++ study's fused kernel in its own semantics).  Later 3.2 libraries add
  * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
- * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes. */
+ * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
+ * bf_vstats_algorithmic_bytes. */
 int bf_abi_version(void);
-/* 1 when this library has the named feature ("incoherent_beam", "beam_detect"), 0 for any other name (and for NULL). */
+/* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats"), 0 for any other name
+ * (and for NULL). */
 int bf_has_feature(const char* name);
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -250,6 +252,33 @@ double bf_incoherent_algorithmic_bytes(int B, int C, int T, int A, int tint, int
 int bf_beam_detect(const void* beams, float* out, int B, int C, int T, int M, int tint, int fint, int flags,
                    float scale, void* stream);
 double bf_detect_algorithmic_bytes(int B, int C, int T, int M, int tint, int fint, int flags);
+
+/* Voltage statistics (no reference counterpart): the first two moments of the sample power of every antenna, pol and
+ * channel over windows of `tint` samples, from the fused operator's own input cube -- the level monitor and the
+ * spectral-kurtosis estimator (Nita & Gary 2010) that tell a caller which inputs to mask or down-weight:
+ *   raw       : 8-bit (B, A, C, T, 2, 2), uint8, or int8 with BF_VSTATS_SIGNED (the sample_signed convention)
+ *   out_power : f32 (B, A, 2, C, T/tint)   out_sk : f32, same shape   out_flags : u8, same shape
+ * Each output may be NULL; at least one must not be.  With n = tint and pw = re^2 + im^2 of one sample of one pol, for
+ * the window t in [j*tint, (j+1)*tint) of (b, a, pol, c):
+ *   S1 = sum pw          S2 = sum pw^2                                                           (exact integers)
+ *   out_power = float32(float64(S1) * float64(scale))                (one float64 multiply, one round-to-nearest-even)
+ *   out_sk    = S1 == 0 ? 0.0f : float32(k * ((nd * float64(S2)) / (float64(S1) * float64(S1)) - 1.0)),
+ *               nd = float64(n), k = (nd + 1) / (nd - 1) computed once on the host in double
+ *   out_flags = (S1 == 0 || out_sk < sk_lo || out_sk > sk_hi) ? 1 : 0    (float32 compares of the stored out_sk; a
+ *               value equal to a limit is not flagged)
+ * Every float64 operation is a separate IEEE operation in exactly that order (no multiply feeds an add), so all three
+ * outputs are bit-exact, independent of the order of summation and deterministic.  out_sk is 1 for Gaussian noise
+ * whatever its level, 0 for a constant-amplitude carrier, far above 1 for pulsed interference, and 0 with the flag set
+ * for a dead input.  B, C, A >= 1, A <= 32768; T % 16 == 0, T <= 2^20; tint is a multiple of 16 that divides T, at
+ * most 2^18 (S2 < 2^52 even for uint8, pw <= 130050: every integer is exact in float64); scale finite and > 0; with
+ * out_flags, 0 <= sk_lo < sk_hi, both finite (ignored without); raw 16-byte, the f32 outputs 4-byte aligned.  Every
+ * output element is written once (no atomics: the outputs need not be zeroed) and the input is never written.
+ * bf_vstats_algorithmic_bytes: `outputs` is a bit mask (1 = power, 2 = sk, 4 = flags); 4*B*A*C*T voltage bytes plus
+ * B*A*2*C*(T/tint) * (4 [power] + 4 [sk] + 1 [flags]) output bytes; 0 for a non-positive argument or an empty mask. */
+#define BF_VSTATS_SIGNED 1
+int bf_voltage_stats(const uint8_t* raw, float* out_power, float* out_sk, uint8_t* out_flags, int B, int C, int T,
+                     int A, int tint, int flags, float scale, float sk_lo, float sk_hi, void* stream);
+double bf_vstats_algorithmic_bytes(int B, int C, int T, int A, int tint, int outputs);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

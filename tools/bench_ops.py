@@ -7,7 +7,9 @@ At cfg2, cfg3 and cfg4 the incoherent beam follows (integration = T and 16, unma
 ceiling for the same read and write bytes (build/libbf_stream.so, `make stream`) measured in the same process;
 `--incoherent` runs only these.  The beam detector follows at the same configurations (f32 and int8 beams of the
 configuration's shape, (tint, fint) = (16, 1) and (T, 16), Stokes I and IQUV), each line with the stream ceiling in the
-same way; `--detect` runs only these.
+same way; `--detect` runs only these.  `--vstats` runs the voltage statistics alone, at cfg3 and cfg4: integration 256
+and 16, all three outputs and the power alone, each line with the stream ceiling for its own bytes, and the incoherent
+beam on the same cube at the same integration, all in one process.
 """
 import argparse
 import ctypes
@@ -24,7 +26,7 @@ import numpy as np  # noqa: E402
 from dpdk_dc_sand_amd import accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, CoeffGeneratorTemplate,  # noqa: E402
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
-                                          PreBeamformReorderTemplate)
+                                          PreBeamformReorderTemplate, VoltageStatsTemplate)
 
 TS = 1 / 1712e6
 HBM = 8.0e12
@@ -35,6 +37,7 @@ CONFIGS = {
     "cfg4": dict(A=256, M=64, C=4096, Ctot=32768, T=256, B=1),
 }
 INCOHERENT_CONFIGS = ("cfg2", "cfg3", "cfg4")
+VSTATS_CONFIGS = ("cfg3", "cfg4")
 
 
 def timeit(queue, fn, reps, settle_s=0.2):
@@ -195,6 +198,36 @@ def run_detect(ctx, q, name, c, reps, rng):
         del beams
 
 
+def run_vstats(ctx, q, name, c, reps, rng):
+    """The voltage statistics over the configuration's voltage cube: integration 256 and 16, all three outputs and the
+    power alone, each with the stream ceiling for its own read and write bytes; then the incoherent beam (unmasked, per
+    pol) on the same cube at the same integration with its own ceiling, in the same process."""
+    A, C, T, B = c["A"], c["C"], c["T"], c["B"]
+    raw = accel.DeviceArray(ctx, (B, A, C, T, 2, 2), np.uint8)
+    raw.set(q, rng.integers(0, 256, raw.shape, dtype=np.uint8))
+
+    def measure(label, tmpl, out_names, tint, **extra):
+        op = tmpl.instantiate(q)
+        op.bind(inSamples=raw)
+        op.ensure_all_bound()
+        t = timeit(q, op, reps)
+        read_bytes, write_bytes = raw.nbytes, sum(op.buffer(n).nbytes for n in out_names)
+        assert tmpl.algorithmic_bytes() == read_bytes + write_bytes
+        ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+        emit(name, label, t, tmpl.algorithmic_bytes(), integration=tint, read_bytes=read_bytes,
+             write_bytes=write_bytes, ceiling_us=round(ct * 1e6, 2),
+             ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+             ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4), **extra)
+
+    for tint in (256, 16):
+        measure(f"vstats_all_tint{tint}", VoltageStatsTemplate(ctx, B, C, T, A, integration=tint,
+                                                               sk_limits=(0.25, 0.55)),
+                ("outPower", "outSK", "outFlags"), tint, outputs="power,sk,flags")
+        measure(f"vstats_power_tint{tint}", VoltageStatsTemplate(ctx, B, C, T, A, integration=tint, sk=False),
+                ("outPower",), tint, outputs="power")
+        measure(f"incoherent_tint{tint}", IncoherentBeamTemplate(ctx, B, C, T, A, integration=tint), ("outData",), tint)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -202,13 +235,17 @@ def main():
     p.add_argument("--fused-only", action="store_true")
     p.add_argument("--incoherent", action="store_true", help="only the incoherent beam and its stream ceiling")
     p.add_argument("--detect", action="store_true", help="only the beam detector and its stream ceiling")
+    p.add_argument("--vstats", action="store_true", help="only the voltage statistics, their stream ceiling and the "
+                   "incoherent beam on the same cube")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
     for name in args.only.split(","):
-        if args.incoherent or args.detect:
+        if args.incoherent or args.detect or args.vstats:
+            if name in VSTATS_CONFIGS and args.vstats:
+                run_vstats(ctx, q, name, CONFIGS[name], args.reps, rng)
             if name in INCOHERENT_CONFIGS and args.incoherent:
                 run_incoherent(ctx, q, name, CONFIGS[name], args.reps, rng)
             if name in INCOHERENT_CONFIGS and args.detect:
