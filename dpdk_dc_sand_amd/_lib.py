@@ -23,6 +23,7 @@ PROTOTYPES = {
     "bf_last_error": (c_char_p, []),
     "bf_abi_version": (c_int, []),
     "bf_has_feature": (c_int, [c_char_p]),
+    "bf_last_kernel": (c_char_p, []),
     "bf_device_count": (c_int, [P_int]),
     "bf_set_device": (c_int, [c_int]),
     "bf_get_device": (c_int, [P_int]),

@@ -658,7 +658,7 @@ int launch_table(const uint8_t* x, const float* w, float* y, long long bpc, int 
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform: grid too large");
   hipLaunchKernelGGL((beamform_table_kernel<Signed, NTS, Vec8>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
                      lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd);
-  BF_LAUNCHED("beamform_table_kernel");
+  BF_LAUNCHED_TAG("beamform_table_kernel", "nts%d,%s", NTS, Vec8 ? "vec8" : "scalar");
 }
 
 template <bool Signed, int NTS, int R>
@@ -679,7 +679,7 @@ int launch_ring(const uint8_t* x, const float* w, float* y, long long bpc, int N
   else
     hipLaunchKernelGGL((beamform_table_ring_kernel<Signed, NTS, R>), dim3(static_cast<unsigned>(grid)),
                        dim3(kThreads), lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd);
-  BF_LAUNCHED("beamform_table_ring_kernel");
+  BF_LAUNCHED_TAG("beamform_table_ring_kernel", "nts%d,r%d,%s", NTS, R, w16 ? "w16" : "w8");
 }
 
 // The persistent ring kernel: UPT table units per thread (Sp * NTS / 4 == UPT), two workgroups per CU.
@@ -700,7 +700,7 @@ int launch_persist(const uint8_t* x, const float* w, float* y, long long bpc, in
   BF_REQUIRE(grid > 0 && (!xcd || grid % 8 == 0), "bf_beamform: persistent grid");
   hipLaunchKernelGGL((beamform_table_persist_kernel<Signed, NTS, R, UPT, G>), dim3(static_cast<unsigned>(grid)),
                      dim3(kThreads), lds, st, x, w, y, NB, A, M, S, NT, nslabs, bpc, xcd, nitems);
-  BF_LAUNCHED("beamform_table_persist_kernel");
+  BF_LAUNCHED_TAG("beamform_table_persist_kernel", "nts%d,r%d,u%d", NTS, R, UPT);
 }
 
 template <bool Signed, int NTS>

@@ -242,7 +242,7 @@ extern "C" int bf_coeff_gen(const float* delay_vals, float* out, int B, int P, i
       hipLaunchKernelGGL(bf::coeff_gen_block_kernel<2>, dim3(gx, static_cast<unsigned>(C), gz), dim3(256), lds,
                          bf::as_stream(stream), dv, out, B * P, C, A, M, na, bpg, base, static_cast<double>(Ctot),
                          sample_period);
-    BF_LAUNCHED("coeff_gen_block_kernel");
+    BF_LAUNCHED_TAG("coeff_gen_block_kernel", "%s", bf::kCoefBlockCache == 0 ? "plain" : "nt");
   }
   if (A >= 32 && M >= 32) {  // many antennas and beams: the tiled, coalesced-read form
     const unsigned gx = static_cast<unsigned>(((A + bf::kCoefTile - 1) / bf::kCoefTile) *
@@ -267,6 +267,9 @@ extern "C" int bf_coeff_gen_time(const float* delay_vals, int delay_channels, vo
              "bf_coeff_gen_time: bad shape");
   BF_REQUIRE(delay_channels == 1 || delay_channels == C, "bf_coeff_gen_time: delay_channels must be 1 or C");
   BF_REQUIRE(sample_period > 0.0, "bf_coeff_gen_time: sample_period must be > 0");
+  BF_REQUIRE((reinterpret_cast<uintptr_t>(delay_vals) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(out) & (out_fp16 ? 3 : 7)) == 0,
+             "bf_coeff_gen_time: misaligned buffer");
   const long long n = static_cast<long long>(n_times) * C * A * M;
   const auto dv = reinterpret_cast<const float4*>(delay_vals);
   const long long base = static_cast<long long>(C) * xeng_id;
@@ -279,7 +282,7 @@ extern "C" int bf_coeff_gen_time(const float* delay_vals, int delay_channels, vo
                        bf::as_stream(stream), dv, delay_channels, out, n_times, C, A, M, base,
                        static_cast<double>(Ctot), sample_period, t0, dt_step);
   }
-  BF_LAUNCHED("coeff_gen_time_kernel");
+  BF_LAUNCHED_TAG("coeff_gen_time_kernel", "%s", out_fp16 ? "f16" : "f32");
 }
 
 extern "C" int bf_coeff_gen_time_study(const float* delay_vals, void* out, int out_fp16, int n_times, int C, int A,
@@ -288,6 +291,7 @@ extern "C" int bf_coeff_gen_time_study(const float* delay_vals, void* out, int o
   BF_REQUIRE(n_times > 0 && C > 0 && A > 0 && M > 0 && fft_size > 0, "bf_coeff_gen_time_study: bad shape");
   BF_REQUIRE(sample_period > 0.0f, "bf_coeff_gen_time_study: sample_period must be > 0");
   BF_REQUIRE((reinterpret_cast<uintptr_t>(delay_vals) & 15) == 0, "bf_coeff_gen_time_study: misaligned delay_vals");
+  BF_REQUIRE((reinterpret_cast<uintptr_t>(out) & (out_fp16 ? 3 : 7)) == 0, "bf_coeff_gen_time_study: misaligned out");
   const long long n = static_cast<long long>(n_times) * C * A * M;
   const auto dv = reinterpret_cast<const float4*>(delay_vals);
   if (out_fp16)
@@ -296,5 +300,5 @@ extern "C" int bf_coeff_gen_time_study(const float* delay_vals, void* out, int o
   else
     hipLaunchKernelGGL(bf::coeff_gen_time_study_kernel<false>, dim3(bf::grid_for(n)), dim3(256), 0,
                        bf::as_stream(stream), dv, out, n_times, C, A, M, sample_period, fft_size);
-  BF_LAUNCHED("coeff_gen_time_study_kernel");
+  BF_LAUNCHED_TAG("coeff_gen_time_study_kernel", "%s", out_fp16 ? "f16" : "f32");
 }

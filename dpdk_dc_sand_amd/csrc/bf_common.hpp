@@ -36,14 +36,21 @@ inline int hip_fail(hipError_t e, const char* what) {
     }                                  \
   } while (0)
 
-// After a kernel launch: report launch-configuration errors without synchronising.
-#define BF_LAUNCHED(name)                                            \
+// bf_last_kernel(): the thread-local name of the kernel the last successful launch on this thread started, as
+// "family" or "family:tag" (tag: printf-formatted, the template instantiation the launcher picked at run time).
+void set_kernel(const char* family, const char* tag_fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// After a kernel launch: report launch-configuration errors without synchronising (error messages carry the plain
+// family name), record the launched kernel for bf_last_kernel().  BF_LAUNCHED_TAG adds the variant tag.
+#define BF_LAUNCHED_TAG(name, ...)                                   \
   do {                                                               \
     hipError_t bf_e_ = hipGetLastError();                            \
     if (bf_e_ != hipSuccess) return ::bf::hip_fail(bf_e_, name);     \
     ::bf::clear_error();                                             \
+    ::bf::set_kernel(name, __VA_ARGS__);                             \
     return BF_OK;                                                    \
   } while (0)
+#define BF_LAUNCHED(name) BF_LAUNCHED_TAG(name, nullptr)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

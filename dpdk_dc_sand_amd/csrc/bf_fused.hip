@@ -995,7 +995,8 @@ int launch_i8_item(FusedArgs P, hipStream_t st, size_t min_lds = 0) {
     hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, true>), grid, block, lds, st, P);
   else
     hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, false>), grid, block, lds, st, P);
-  BF_LAUNCHED("beamform_fused_i8_item_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_i8_item_kernel", "nts%d,%s,%s,%s", NTS, Full ? "full" : "partial",
+                  a64 ? "a64" : "aany", pow2 ? "pow2" : "anyscale");
 }
 
 template <bool Signed>
@@ -1022,6 +1023,7 @@ int launch_i8(FusedArgs P, hipStream_t st) {
     BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
     hipLaunchKernelGGL((beamform_fused_i8_kernel<Signed, 2>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
                        lds_bytes(2), st, P);
+    BF_LAUNCHED_TAG("beamform_fused_i8_kernel", "nts2");
   } else {
     BF_REQUIRE(lds_bytes(1) <= kMaxLds, "bf_beamform_fused: n_ants=%d too large", P.A);
     P.nslabs = P.NT;
@@ -1030,7 +1032,7 @@ int launch_i8(FusedArgs P, hipStream_t st) {
     hipLaunchKernelGGL((beamform_fused_i8_kernel<Signed, 1>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
                        lds_bytes(1), st, P);
   }
-  BF_LAUNCHED("beamform_fused_i8_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_i8_kernel", "nts1");
 }
 
 template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32, int Occ, bool Pow2>
@@ -1044,7 +1046,9 @@ int launch_item_k(FusedArgs P, hipStream_t st) {
   BF_REQUIRE(n_items < (1LL << 31), "bf_beamform_fused: too many (batch, channel) items");
   hipLaunchKernelGGL((beamform_fused_item_kernel<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, Pow2>),
                      dim3(static_cast<unsigned>(n_items)), dim3(kThreads), lds, st, P);
-  BF_LAUNCHED("beamform_fused_item_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_item_kernel", "%s,nts%d,%s,%s%s%s", OutI8 ? "i8" : "f32", NTS,
+                  Full ? "full" : "partial", Exact ? "exact" : "fast", StagedF32 ? ",staged" : "",
+                  !OutI8 ? "" : Pow2 ? ",pow2" : ",anyscale");
 }
 
 template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32 = false, int Occ = 1>
@@ -1068,7 +1072,7 @@ int launch_generic(FusedArgs P, hipStream_t st) {
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
   hipLaunchKernelGGL((beamform_fused_kernel<Signed, OutI8, NTS, Exact>), dim3(static_cast<unsigned>(grid)),
                      dim3(kThreads), lds, st, P);
-  BF_LAUNCHED("beamform_fused_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_kernel", "%s,nts%d,%s", OutI8 ? "i8" : "f32", NTS, Exact ? "exact" : "fast");
 }
 
 template <bool Signed, bool OutI8, bool Exact>
@@ -1153,6 +1157,7 @@ extern "C" int bf_beamform_fused_ws(const uint8_t* raw, const float* delay_vals,
   BF_REQUIRE((reinterpret_cast<uintptr_t>(raw) & 15) == 0 && (reinterpret_cast<uintptr_t>(delay_vals) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(y) & 15) == 0,
              "bf_beamform_fused: misaligned buffer");
+  BF_REQUIRE((reinterpret_cast<uintptr_t>(gains) & 3) == 0, "bf_beamform_fused: misaligned gains");
   bf::FusedArgs P{};
   P.raw = raw;
   P.dv = reinterpret_cast<const float4*>(delay_vals);

@@ -295,7 +295,7 @@ extern "C" double bf_incoherent_algorithmic_bytes(int B, int C, int T, int A, in
 
 extern "C" int bf_has_feature(const char* name) {
   return name && (std::strcmp(name, "incoherent_beam") == 0 || std::strcmp(name, "beam_detect") == 0 ||
-                  std::strcmp(name, "voltage_stats") == 0)
+                  std::strcmp(name, "voltage_stats") == 0 || std::strcmp(name, "last_kernel") == 0)
              ? 1
              : 0;
 }

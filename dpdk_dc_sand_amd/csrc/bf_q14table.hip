@@ -217,7 +217,7 @@ int launch_q14_table(const FusedArgs& P, uint32_t* out, int layout, hipStream_t 
   else
     hipLaunchKernelGGL(q14_table_kernel<false>, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy), P.B),
                        dim3(256), 0, st, Q);
-  BF_LAUNCHED("q14_table_kernel");
+  BF_LAUNCHED_TAG("q14_table_kernel", "%s,%s", P.gain ? "gain" : "unit", layout == kLayoutNatural ? "natural" : "w32");
 }
 
 }  // namespace bf
@@ -233,6 +233,7 @@ extern "C" int bf_q14_coeffs(const float* delay_vals, int delay_channels, const 
   BF_REQUIRE(sample_period > 0.0, "bf_q14_coeffs: sample_period must be > 0");
   BF_REQUIRE((reinterpret_cast<uintptr_t>(delay_vals) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
              "bf_q14_coeffs: misaligned buffer");
+  BF_REQUIRE((reinterpret_cast<uintptr_t>(gains) & 3) == 0, "bf_q14_coeffs: misaligned gains");
   bf::FusedArgs P{};
   P.dv = reinterpret_cast<const float4*>(delay_vals);
   P.gain = gains;

@@ -178,5 +178,5 @@ extern "C" int bf_reorder(const uint8_t* in, uint8_t* out, int B, int A, int C, 
   else
     bf::launch_reorder<false>(cache, dim3(static_cast<unsigned>(grid)), lds, bf::as_stream(stream), in, out, A, C, T,
                               TT, nchunk, xcd_range);
-  BF_LAUNCHED("reorder_kernel");
+  BF_LAUNCHED_TAG("reorder_kernel", "%s", A % 8 == 0 ? "oct" : "any");
 }

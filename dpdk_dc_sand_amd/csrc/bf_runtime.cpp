@@ -22,6 +22,20 @@ void set_error(const char* fmt, ...) {
 
 void clear_error() { g_last_error.clear(); }
 
+static thread_local std::string g_last_kernel;
+
+void set_kernel(const char* family, const char* tag_fmt, ...) {
+  g_last_kernel = family;
+  if (!tag_fmt) return;
+  char buf[128];
+  va_list ap;
+  va_start(ap, tag_fmt);
+  vsnprintf(buf, sizeof(buf), tag_fmt, ap);
+  va_end(ap);
+  g_last_kernel += ':';
+  g_last_kernel += buf;
+}
+
 // An empty kernel whose dispatches delimit a region in a profiler's kernel trace (bench.py: the timed steps).
 __global__ void bf_trace_mark_kernel(int tag) { (void)tag; }
 
@@ -78,6 +92,8 @@ int cu_count() {
 extern "C" {
 
 const char* bf_last_error(void) { return bf::g_last_error.c_str(); }
+
+const char* bf_last_kernel(void) { return bf::g_last_kernel.c_str(); }
 
 // 3.0: 0x0500 (BF_FUSED_PATH_WIDE16), accepted by 2.0, is rejected; bf_coeff_gen_time_study, bf_comm_stats,
 // bf_comm_load and bf_checksum added; the root's own scatter slice is a 2-D copy at N > 1 (include/bf.h).

@@ -932,7 +932,7 @@ int launch_w32r_contract(FusedArgs P, hipStream_t st) {
   BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
   hipLaunchKernelGGL((beamform_fused_i8_w32r_kernel<Pow2>), dim3(static_cast<unsigned>(grid)), dim3(kW8Threads), 0,
                      st, P);
-  BF_LAUNCHED("beamform_fused_i8_w32r_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_i8_w32r_kernel", "%s", Pow2 ? "pow2" : "anyscale");
 }
 
 template <bool Signed>
@@ -960,7 +960,7 @@ int launch_w32(FusedArgs P, hipStream_t st) {
   else
     hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, false>), dim3(static_cast<unsigned>(grid)),
                        dim3(kW8Threads), lds, st, P);
-  BF_LAUNCHED("beamform_fused_i8_w32_kernel");
+  BF_LAUNCHED_TAG("beamform_fused_i8_w32_kernel", "%s", P.gain ? "gain" : "unit");
 }
 
 // The table-driven contraction of one launch (or channel chunk: P.c_count, pointers offset by the caller) whose
@@ -994,7 +994,8 @@ int launch_w32t_contract(FusedArgs P, hipStream_t st) {
                          grid3, block, lds, st, P);
     else  // offsets past 2^31 (A C T 4 >= 2 GiB): the pointer form
       hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false>), grid3, block, lds, st, P);
-    BF_LAUNCHED("beamform_fused_i8_w32t_kernel");
+    BF_LAUNCHED_TAG("beamform_fused_i8_w32t_kernel", "%s",
+                    straight && buf ? (pow2 ? "straight,pow2" : "straight,anyscale") : buf ? "general,buf" : "general,ptr");
   }
 }
 

@@ -39,11 +39,35 @@ const char* bf_last_error(void);
  * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
- * bf_vstats_algorithmic_bytes. */
+ * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel. */
 int bf_abi_version(void);
-/* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats"), 0 for any other name
- * (and for NULL). */
+/* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel"), 0 for
+ * any other name (and for NULL). */
 int bf_has_feature(const char* name);
+/* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
+ * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
+ * name carries the choice after a colon ("beamform_fused_i8_item_kernel:nts2,full,a64,pow2",
+ * "beamform_table_ring_kernel:nts4,r16,w16"): tests and measurements use it to know which device code a call ran.  An
+ * entry point that launches two kernels (bf_beamform_fused_ws with a workspace: the table generator, then the
+ * contraction) reports the last.  The spelling of names and tags is not part of the ABI. */
+const char* bf_last_kernel(void);
+
+/* Pointer alignment.  Every compute entry point checks the alignment of its device pointers before it launches and
+ * returns BF_ERR_ARG ("misaligned" / "aligned" in bf_last_error) otherwise; hipMalloc'd buffers satisfy all of them.
+ * Bytes:
+ *   bf_coeff_gen                      delay_vals 16, out 8 (16 selects the faster block form)
+ *   bf_coeff_gen_time                 delay_vals 16, out 8 (float2) or 4 (half2, out_fp16)
+ *   bf_coeff_gen_time_study           delay_vals 16, out 8 (float2) or 4 (half2, out_fp16)
+ *   bf_beamform_study_single_channel  delay_vals 16, x 4, out 8
+ *   bf_reorder                        in 16, out 16
+ *   bf_beamform                       x 8, w 4, y 16 (x and w at 16 select the faster forms)
+ *   bf_beamform_fused*                raw 16, delay_vals 16, y 16, gains 4 (or NULL), workspace 16 (or NULL)
+ *   bf_q14_coeffs                     delay_vals 16, gains 4 (or NULL), out 4
+ *   bf_requant                        y 16, q 4
+ *   bf_incoherent_beam                raw 16, ant_mask 1 (none), out 4
+ *   bf_beam_detect                    beams 16, out 4
+ *   bf_voltage_stats                  raw 16, out_power 4, out_sk 4, out_flags 1 (none)
+ *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
  * The reference gets these from katsdpsigproc.accel / PyCUDA (accel.create_some_context,
@@ -208,7 +232,9 @@ int bf_beamform_fused_ws(const uint8_t* raw, const float* delay_vals, int delay_
 int bf_q14_coeffs(const float* delay_vals, int delay_channels, const float* gains, uint32_t* out, int B, int C, int A,
                   int M, int Ctot, int xeng_id, double sample_period, double t0, double batch_dt, void* stream);
 
-/* 8-bit requantiser (no reference counterpart; SURVEY §7 build step 7): q = clamp(rne(y*scale), -127, 127). */
+/* 8-bit requantiser (no reference counterpart; SURVEY §7 build step 7): q = clamp(rne(y*scale), -127, 127), the product
+ * one float32 rounding.  +-inf saturate to +-127.  A NaN (a NaN input, or inf * 0) gives -127: the clamp is
+ * min(max(r, -127), 127) with IEEE maxNum / minNum, which drop the NaN operand.  y 16-byte, q 4-byte aligned. */
 int bf_requant(const float* y, int8_t* q, size_t n, float scale, void* stream);
 
 /* Incoherent beam (no reference counterpart): the power re^2 + im^2 of every antenna, summed over a set of antennas

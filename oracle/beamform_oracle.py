@@ -165,8 +165,11 @@ def dot_magnitude(x, w, signed=False):
 
 def requantise(y, scale):
     """8-bit requantiser contract (the reference has none; SURVEY hard part 5): round-half-to-even of
-    y * scale, saturated to [-127, 127] (symmetric, so conjugation never overflows).  int8 output."""
-    v = np.rint(np.asarray(y, np.float32) * np.float32(scale))
+    y * scale (one float32 product), saturated to [-127, 127] (symmetric, so conjugation never overflows).  A NaN
+    product gives -127 (include/bf.h: the clamp's maxNum(r, -127) drops the NaN).  int8 output."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.rint(np.asarray(y, np.float32) * np.float32(scale))
+    v = np.where(np.isnan(v), np.float32(-127), v)
     return np.clip(v, -127, 127).astype(np.int8)
 
 
