@@ -67,6 +67,8 @@ PROTOTYPES = {
     "bf_beamform_fused_ws": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_float, c_void_p,
                                      c_size_t, c_void_p]),
+    "bf_fused_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_size_t, c_int,
+                              c_void_p]),
     "bf_q14_coeffs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_double, c_double, c_double, c_void_p]),
     "bf_pipeline_create": (c_int, [P_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int,
@@ -161,6 +163,21 @@ def call(name, *args):
     if st != 0:
         raise BeamformerError(name, st, lib.bf_last_error().decode(errors="replace"))
     return st
+
+
+class FusedPlanInfo(ctypes.Structure):
+    """bf_fused_plan_info (include/bf.h)."""
+    _fields_ = [("kernel", ctypes.c_char * 96), ("uses_table", c_int), ("nslabs", c_int), ("xcd_order", c_int),
+                ("ch_run", c_int), ("grid", ctypes.c_uint), ("block", ctypes.c_uint), ("lds_bytes", c_size_t),
+                ("workspace_bytes", c_size_t)]
+
+
+def fused_plan(B, C, T, A, M, delay_channels=1, has_gains=False, flags=0, out_scale=1.0, workspace_bytes=0, cus=0):
+    """The launch bf_beamform_fused_ws would make (bf_fused_plan: pure host code, no GPU needed)."""
+    info = FusedPlanInfo()
+    call("bf_fused_plan", B, C, T, A, M, delay_channels, int(has_gains), flags, out_scale, workspace_bytes, cus,
+         ctypes.byref(info))
+    return info
 
 
 def ptr(x):

@@ -708,14 +708,18 @@ int dispatch_vec(const uint8_t* x, const float* w, float* y, long long bpc, int 
                  hipStream_t st) {
   if (A % 4 == 0) {
     // ring depth: the k-steps of a row, up to 16 (the steps are padded to a multiple of R); long rows only
-    if (S >= 16 && coef_lds_bytes((S + 15) / 16 * 16, NTS) <= kMaxLds) {
-      // 256-antenna rows in two-workgroup slabs (config 4): the persistent form, the next slab loaded under the
-      // current item's contraction
-      if constexpr (NTS == 2)
-        if ((S + 15) / 16 == 1 && A % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-            (bpc >= 8))
-          return launch_persist<Signed, 2, 16, 8>(x, w, y, bpc, NB, A, M, S, NT, st);
-      return launch_ring<Signed, NTS, 16>(x, w, y, bpc, NB, A, M, S, NT, st);
+    // (slabs of one or two tiles only: 16 k-steps of four tiles are 128 KiB, which dispatch_table gives to two-tile
+    // slabs before it would come here, and 16 k-steps of eight tiles exceed LDS)
+    if constexpr (NTS <= 2) {
+      if (S >= 16 && coef_lds_bytes((S + 15) / 16 * 16, NTS) <= kMaxLds) {
+        // 256-antenna rows in two-workgroup slabs (config 4): the persistent form, the next slab loaded under the
+        // current item's contraction
+        if constexpr (NTS == 2)
+          if ((S + 15) / 16 == 1 && A % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+              (bpc >= 8))
+            return launch_persist<Signed, 2, 16, 8>(x, w, y, bpc, NB, A, M, S, NT, st);
+        return launch_ring<Signed, NTS, 16>(x, w, y, bpc, NB, A, M, S, NT, st);
+      }
     }
     if (S >= 8 && coef_lds_bytes((S + 7) / 8 * 8, NTS) <= kMaxLds)
       return launch_ring<Signed, NTS, 8>(x, w, y, bpc, NB, A, M, S, NT, st);

@@ -24,14 +24,6 @@
 
 namespace bf {
 
-constexpr int kGroup = 4;  // k-steps per register-resident load group (64 antennas)
-
-// Staged float-beam stores (the item kernel's StagedF32 form): each wave's 8 KiB (64 rows x 128 B, one slab = the
-// whole row) staged through a padded wave-private LDS image and written as 1 KiB contiguous pieces per store
-// instruction.
-constexpr int kF32StageRow = 36;                        // floats per staged row (32 + 4: 4-way write conflicts)
-constexpr size_t kF32StageBytes = 4 * 64 * kF32StageRow * 4;  // 4 waves x 64 rows
-
 // Workgroup -> (batch, channel) of an item kernel.  Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8),
 // so with channel-fastest numbering every XCD reads every 8th KiB run of each antenna stream.  XCD-range order
 // gives XCD x the contiguous channel range [x C/8, (x+1) C/8), channel fastest within it and batches outermost:
@@ -968,142 +960,69 @@ __global__ __launch_bounds__(kThreads, Occ) void beamform_fused_i8_item_kernel(F
   }
 }
 
-// Workgroup order of the item kernels (item_coords): XCD-range when C % 8 == 0 and the beams are at least 8 (config
-// 3: 450-461 -> 432-433 us); channel-fastest for one or two beams, whose read-dominated traffic measured no better
-// that way (config 2: 334-357 vs 332-340 us, profiles/r1_v8_order_bench_ab.txt).  BF_FUSED_ORDER_XCD / _CHANNEL force.
-bool item_xcd_order(const FusedArgs& P) {
-  if (P.order == BF_FUSED_ORDER_CHANNEL) return false;
-  if (P.order == BF_FUSED_ORDER_XCD) return (P.C & 7) == 0;
-  return (P.C & 7) == 0 && P.M >= 8;
+// ---------------------------------------------------------------------------------------------------------
+// Launching a plan (bf_fused_plan.cpp decides; nothing below looks at a shape).
+int launch_planned(FusedKernel k, const FusedPlan& p, FusedArgs P, hipStream_t st) {
+  P.nslabs = p.nslabs;
+  P.xcd_order = p.xcd_order;
+  P.ch_run = p.ch_run;
+  hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.block), p.lds, st, P);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, fused_family_name(p.family));
+  char name[128];
+  fused_plan_name(p, name, sizeof(name));
+  clear_error();
+  set_kernel(name, nullptr);
+  return BF_OK;
 }
 
-template <bool Signed, int NTS, bool Full, int Occ = 3>
-int launch_i8_item(FusedArgs P, hipStream_t st, size_t min_lds = 0) {
-  P.nslabs = (P.NT + NTS - 1) / NTS;
-  P.xcd_order = item_xcd_order(P);
-  const size_t lds = std::max<size_t>(static_cast<size_t>(2) * NTS * 2 * 64 * 16 + 4 * 32 * 4, min_lds);
-  const long long n_items = static_cast<long long>(P.nslabs) * P.B * P.C;
-  BF_REQUIRE(n_items < (1LL << 31), "bf_beamform_fused: too many items");
-  const bool a64 = P.A == 64 && 24ull * P.C * P.T * 4 + P.T * 4ull < (1ull << 32);
-  const bool pow2 = scale_is_pow2(P.out_scale * 0x1p-14f);  // the requantisation's exact single FMA
-  const dim3 grid(static_cast<unsigned>(n_items)), block(kThreads);
-  if (a64 && pow2)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, true, true>), grid, block, lds, st, P);
-  else if (a64)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, true, false>), grid, block, lds, st, P);
-  else if (pow2)
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, true>), grid, block, lds, st, P);
-  else
-    hipLaunchKernelGGL((beamform_fused_i8_item_kernel<Signed, NTS, Full, Occ, false, false>), grid, block, lds, st, P);
-  BF_LAUNCHED_TAG("beamform_fused_i8_item_kernel", "nts%d,%s,%s,%s", NTS, Full ? "full" : "partial",
-                  a64 ? "a64" : "aany", pow2 ? "pow2" : "anyscale");
-}
-
+// The integer kernels of this file (I8Item, I8Generic).  The item kernel runs at 3 waves per SIMD (4 spills).
 template <bool Signed>
-int launch_i8(FusedArgs P, hipStream_t st) {
-  const int S8 = (2 * P.A + 63) / 64;
-  const int choice = fused_kernel_choice(P);
-  const bool small = S8 <= 2 && P.T <= 256;
-  // the 32-beam slab kernels up to A = 512 (their Q14 limb image in LDS); beyond, the generic kernel (groups of 64
-  // antennas).  (The round-1 16-beam slab kernel, which also covered 512 < A <= 724, was removed with the diagnostic build.)
-  if ((choice == BF_FUSED_PATH_WIDE || (choice == 0 && !small)) && i8_w32_fits(P)) return launch_i8_w32<Signed>(P, st);
-  if (small && choice != BF_FUSED_PATH_GENERIC) {
-    const int M2 = 2 * P.M;
-    if (P.NT >= 2) {
-      if (M2 % 32 == 0) return launch_i8_item<Signed, 2, true>(P, st);
-      return launch_i8_item<Signed, 2, false>(P, st);
-    }
-    if (M2 == 16) return launch_i8_item<Signed, 1, true>(P, st);
-    return launch_i8_item<Signed, 1, false>(P, st);
-  }
-  auto lds_bytes = [&](int nts) { return static_cast<size_t>(S8) * nts * 2 * 64 * 16 + nts * 16 * 4; };
-  if (P.NT >= 2 && lds_bytes(2) <= kMaxLds) {
-    P.nslabs = (P.NT + 1) / 2;
-    const long long grid = static_cast<long long>(P.B) * P.C * P.nslabs;
-    BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-    hipLaunchKernelGGL((beamform_fused_i8_kernel<Signed, 2>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
-                       lds_bytes(2), st, P);
-    BF_LAUNCHED_TAG("beamform_fused_i8_kernel", "nts2");
-  } else {
-    BF_REQUIRE(lds_bytes(1) <= kMaxLds, "bf_beamform_fused: n_ants=%d too large", P.A);
-    P.nslabs = P.NT;
-    const long long grid = static_cast<long long>(P.B) * P.C * P.nslabs;
-    BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-    hipLaunchKernelGGL((beamform_fused_i8_kernel<Signed, 1>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
-                       lds_bytes(1), st, P);
-  }
-  BF_LAUNCHED_TAG("beamform_fused_i8_kernel", "nts1");
+FusedKernel q14_kernel(const FusedPlan& p) {
+  if (p.family == FusedFamily::I8Item)
+    return with_bools([](auto two, auto full, auto a64, auto pow2) -> FusedKernel {
+      return beamform_fused_i8_item_kernel<Signed, two.value ? 2 : 1, full.value, 3, a64.value, pow2.value>;
+    }, p.nts == 2, p.full, p.a64, p.pow2);
+  return with_bools([](auto two) -> FusedKernel { return beamform_fused_i8_kernel<Signed, two.value ? 2 : 1>; },
+                    p.nts == 2);
 }
 
-template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32, int Occ, bool Pow2>
-int launch_item_k(FusedArgs P, hipStream_t st) {
-  P.nslabs = (P.NT + NTS - 1) / NTS;
-  P.xcd_order = item_xcd_order(P);
-  if constexpr (StagedF32)
-    BF_REQUIRE(!OutI8 && Full && NTS == 2 && P.M == 16 && P.T <= 256, "item kernel: staged f32 stores need M == 16");
-  const size_t lds = coef_lds_bytes(P.S, NTS) + (StagedF32 ? kF32StageBytes : 0);
-  const long long n_items = static_cast<long long>(P.nslabs) * P.B * P.C;
-  BF_REQUIRE(n_items < (1LL << 31), "bf_beamform_fused: too many (batch, channel) items");
-  hipLaunchKernelGGL((beamform_fused_item_kernel<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, Pow2>),
-                     dim3(static_cast<unsigned>(n_items)), dim3(kThreads), lds, st, P);
-  BF_LAUNCHED_TAG("beamform_fused_item_kernel", "%s,nts%d,%s,%s%s%s", OutI8 ? "i8" : "f32", NTS,
-                  Full ? "full" : "partial", Exact ? "exact" : "fast", StagedF32 ? ",staged" : "",
-                  !OutI8 ? "" : Pow2 ? ",pow2" : ",anyscale");
-}
-
-template <bool Signed, bool OutI8, int NTS, bool Exact, bool Full, bool StagedF32 = false, int Occ = 1>
-int launch_item(FusedArgs P, hipStream_t st) {
-  if constexpr (OutI8) {
-    // a power-of-two scale: the float path's requantisation as one exact FMA (its round-4 two-rounding form had
-    // cost cfg3 int8-via-f32 ~3 %, BENCH_r03 460.8 -> BENCH_r04 476.3 us; A/B in DESIGN §5)
-    if (scale_is_pow2(P.out_scale)) return launch_item_k<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, true>(P, st);
-  }
-  return launch_item_k<Signed, OutI8, NTS, Exact, Full, StagedF32, Occ, false>(P, st);
-}
-
-template <bool Signed, bool OutI8, int NTS, bool Exact>
-int launch_generic(FusedArgs P, hipStream_t st) {
-  P.nslabs = (P.NT + NTS - 1) / NTS;
-  const size_t lds = coef_lds_bytes(P.S, NTS);
-  BF_REQUIRE(lds <= kMaxLds, "bf_beamform_fused: n_ants=%d too large", P.A);
-  P.xcd_order = P.nslabs > 1 && P.order != BF_FUSED_ORDER_CHANNEL;
-  const long long items = static_cast<long long>(P.B) * P.C;
-  const long long grid = P.xcd_order ? (items + 7) / 8 * 8 * P.nslabs : items * P.nslabs;
-  BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-  hipLaunchKernelGGL((beamform_fused_kernel<Signed, OutI8, NTS, Exact>), dim3(static_cast<unsigned>(grid)),
-                     dim3(kThreads), lds, st, P);
-  BF_LAUNCHED_TAG("beamform_fused_kernel", "%s,nts%d,%s", OutI8 ? "i8" : "f32", NTS, Exact ? "exact" : "fast");
-}
-
+// The float contractions of this file (Item, Generic); OutI8: their beams requantised in the kernel.
 template <bool Signed, bool OutI8, bool Exact>
-int dispatch(FusedArgs P, hipStream_t st) {
-  const int choice = fused_kernel_choice(P);
-  const bool small = P.S <= kGroup && P.T <= 256;
-  if constexpr (!OutI8) {
-    // many antennas x beams (config 4): the wide kernel keeps every beam of the item in one workgroup
-    const bool wide = choice == BF_FUSED_PATH_WIDE || (choice == 0 && P.M >= 24 && (!small || P.M > 32));
-    if (wide && wide_fits(P)) return launch_wide<Signed, Exact>(P, st);
-  }
-  if (small && choice != BF_FUSED_PATH_GENERIC) {
+FusedKernel f32_kernel(const FusedPlan& p) {
+  if (p.family == FusedFamily::Item) {
     // int8 beams from the float path: bounded to 4 waves per SIMD (124 VGPRs, no spills; cfg3 489 -> 465 us,
     // profiles/r3_i_cfg3_f32contract_ablation.txt); float32 beams keep the unbounded form (816 vs 811 us)
     constexpr int kOcc = OutI8 ? 4 : 1;
-    const int M2 = 2 * P.M;
-    if (P.NT >= 2) {
-      // float beams of 16 beams (config 3): 1 KiB contiguous non-temporal stores staged through LDS, 807 -> 784 us
-      // same process (profiles/r3_v_f32_staged_stores.txt, r3_x_f32_staged_ab.txt)
-      if constexpr (!OutI8)
-        if (P.M == 16 && P.T <= 256) return launch_item<Signed, false, 2, Exact, true, true>(P, st);
-      if (M2 % 32 == 0) return launch_item<Signed, OutI8, 2, Exact, true, false, kOcc>(P, st);
-      return launch_item<Signed, OutI8, 2, Exact, false, false, kOcc>(P, st);
-    }
-    if (M2 == 16) return launch_item<Signed, OutI8, 1, Exact, true, false, kOcc>(P, st);
-    return launch_item<Signed, OutI8, 1, Exact, false, false, kOcc>(P, st);
+    // float beams of 16 beams (config 3): 1 KiB contiguous non-temporal stores staged through LDS, 807 -> 784 us
+    // same process (profiles/r3_v_f32_staged_stores.txt, r3_x_f32_staged_ab.txt)
+    if constexpr (!OutI8)
+      if (p.staged) return beamform_fused_item_kernel<Signed, false, 2, Exact, true, true>;
+    // a power-of-two scale: the float path's requantisation as one exact FMA (its round-4 two-rounding form had
+    // cost cfg3 int8-via-f32 ~3 %, BENCH_r03 460.8 -> BENCH_r04 476.3 us; A/B in DESIGN §5)
+    return with_bools([](auto two, auto full, auto pow2) -> FusedKernel {
+      return beamform_fused_item_kernel<Signed, OutI8, two.value ? 2 : 1, Exact, full.value, false, kOcc,
+                                        OutI8 && pow2.value>;
+    }, p.nts == 2, p.full, p.pow2);
   }
-  const int want = 2;  // the generic kernel's widest slab
-  if (want >= 4 && P.NT >= 4 && coef_lds_bytes(P.S, 4) <= kMaxLds) return launch_generic<Signed, OutI8, 4, Exact>(P, st);
-  if (want >= 2 && P.NT >= 2 && coef_lds_bytes(P.S, 2) <= kMaxLds) return launch_generic<Signed, OutI8, 2, Exact>(P, st);
-  return launch_generic<Signed, OutI8, 1, Exact>(P, st);
+  return with_bools([](auto two) -> FusedKernel { return beamform_fused_kernel<Signed, OutI8, two.value ? 2 : 1, Exact>; },
+                    p.nts == 2);
+}
+
+int launch_fused(const FusedPlan& p, FusedArgs P, hipStream_t st) {
+  switch (p.family) {
+    case FusedFamily::Wide:
+    case FusedFamily::WideP2: return launch_wide(p, P, st);
+    case FusedFamily::W32:
+    case FusedFamily::W32T:
+    case FusedFamily::W32R: return launch_w32(p, P, st);
+    case FusedFamily::I8Item:
+    case FusedFamily::I8Generic: return launch_planned(p.sgn ? q14_kernel<true>(p) : q14_kernel<false>(p), p, P, st);
+    default:
+      return launch_planned(with_bools([&](auto sgn, auto i8, auto exact) -> FusedKernel {
+                              return f32_kernel<sgn.value, i8.value, exact.value>(p);
+                            }, p.sgn, p.i8out, p.exact), p, P, st);
+  }
 }
 
 }  // namespace bf
@@ -1123,22 +1042,36 @@ extern "C" int bf_beamform_fused_weighted(const uint8_t* raw, const float* delay
                               t0, batch_dt, flags, out_scale, nullptr, 0, stream);
 }
 
-// The workspace the automatic path of bf_beamform_fused_ws can use: the int8 wide path's Q14 coefficient table
-// (bf_q14table.hip) when the shape takes the 32-beam int8 kernel, else 0.
+// The workspace the automatic path of bf_beamform_fused_ws can use: the Q14 coefficient table (bf_q14table.hip) of
+// the plan that an unlimited workspace gives, else 0.
 extern "C" int bf_fused_workspace_bytes(int B, int C, int T, int A, int M, int flags, size_t* bytes) {
   BF_REQUIRE(bytes != nullptr, "bf_fused_workspace_bytes: null pointer");
   *bytes = 0;
   BF_REQUIRE(B > 0 && C > 0 && T > 0 && A > 0 && M > 0, "bf_fused_workspace_bytes: bad shape");
   const char* ferr = bf::fused_flags_error(flags);
   BF_REQUIRE(ferr == nullptr, "bf_fused_workspace_bytes: %s (flags 0x%x)", ferr, flags);
-  const int path = flags & BF_FUSED_PATH_MASK;
-  if ((flags & BF_FUSED_OUT_INT8) && !(flags & BF_FUSED_INT8_VIA_F32) && (path == 0 || path == BF_FUSED_PATH_WIDE)) {
-    bf::FusedArgs P{};
-    P.B = B, P.C = C, P.T = T, P.A = A, P.M = M;
-    const bool small = (2 * A + 63) / 64 <= 2 && T <= 256;
-    if ((path == BF_FUSED_PATH_WIDE || !small) && bf::i8_w32_fits(P) && bf::w32_table_fits(A))
-      *bytes = bf::w32_table_bytes(B, C, A, M);
-  }
+  *bytes = bf::plan_fused({B, C, T, A, M, 1, false, flags, 1.0f, SIZE_MAX, 1}).table_bytes;
+  return BF_OK;
+}
+
+extern "C" int bf_fused_plan(int B, int C, int T, int A, int M, int delay_channels, int has_gains, int flags,
+                             float out_scale, size_t workspace_bytes, int cus, bf_fused_plan_info* out) {
+  BF_REQUIRE(out != nullptr, "bf_fused_plan: null pointer");
+  *out = bf_fused_plan_info{};
+  BF_REQUIRE(B > 0 && C > 0 && T > 0 && A > 0 && M > 0 && T % bf::kSamplesPerBlock == 0 && cus >= 0 &&
+                 (delay_channels == 1 || delay_channels == C),
+             "bf_fused_plan: bad shape B=%d C=%d T=%d A=%d M=%d delay_channels=%d", B, C, T, A, M, delay_channels);
+  const char* ferr = bf::fused_flags_error(flags);
+  BF_REQUIRE(ferr == nullptr, "bf_fused_plan: %s (flags 0x%x)", ferr, flags);
+  const bf::FusedPlan p = bf::plan_fused({B, C, T, A, M, delay_channels, has_gains != 0, flags, out_scale,
+                                          workspace_bytes, cus ? cus : bf::cu_count()});
+  BF_REQUIRE(p.status == BF_OK, "%s", p.error);
+  bf::fused_plan_name(p, out->kernel, sizeof(out->kernel));
+  out->uses_table = p.table;
+  out->grid = p.grid, out->block = p.block;
+  out->nslabs = p.nslabs, out->xcd_order = p.xcd_order, out->ch_run = p.ch_run;
+  out->lds_bytes = p.lds, out->workspace_bytes = p.table_bytes;
+  bf::clear_error();
   return BF_OK;
 }
 
@@ -1158,12 +1091,12 @@ extern "C" int bf_beamform_fused_ws(const uint8_t* raw, const float* delay_vals,
                  (reinterpret_cast<uintptr_t>(y) & 15) == 0,
              "bf_beamform_fused: misaligned buffer");
   BF_REQUIRE((reinterpret_cast<uintptr_t>(gains) & 3) == 0, "bf_beamform_fused: misaligned gains");
+  BF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "bf_beamform_fused: misaligned workspace");
   bf::FusedArgs P{};
   P.raw = raw;
   P.dv = reinterpret_cast<const float4*>(delay_vals);
   P.gain = gains;
   P.y = y;
-  BF_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "bf_beamform_fused: misaligned workspace");
   P.table = static_cast<const uint32_t*>(workspace);
   P.table_bytes = workspace ? workspace_bytes : 0;
   P.delay_channels = delay_channels;
@@ -1183,24 +1116,10 @@ extern "C" int bf_beamform_fused_ws(const uint8_t* raw, const float* delay_vals,
   P.out_scale = out_scale;
   P.path = flags & BF_FUSED_PATH_MASK;
   P.order = flags & BF_FUSED_ORDER_MASK;
-  hipStream_t st = bf::as_stream(stream);
-  const bool sgn = flags & BF_FUSED_SIGNED, i8 = flags & BF_FUSED_OUT_INT8, ex = flags & BF_FUSED_EXACT_COEFF;
-  // int8 beams: the Q14 integer contract (default), or requantised float beams (BF_FUSED_INT8_VIA_F32)
-  if (i8 && !(flags & BF_FUSED_INT8_VIA_F32)) {
-    // The contract's int32 sum: |y| <= A * max|x| * (|Wc| + |Ws|) with |Wc| + |Ws| <= sqrt(2) * 2^14 + 1 = 23171 at
-    // unit gain.  Beyond that the int32 accumulators would wrap (the oracle sums in int64): refuse.  With gains the
-    // caller, which owns the weights, checks the bound (FusedBeamformerTemplate.check_weights).
-    BF_REQUIRE(gains || static_cast<double>(A) * (sgn ? 128 : 255) * 23171.0 < 2147483648.0,
-               "bf_beamform_fused: n_ants=%d overflows the int8 path's int32 beam sums (%s samples); use float beams "
-               "or BF_FUSED_INT8_VIA_F32", A, sgn ? "int8" : "uint8");
-    return sgn ? bf::launch_i8<true>(P, st) : bf::launch_i8<false>(P, st);
-  }
-  if (sgn) {
-    if (i8) return ex ? bf::dispatch<true, true, true>(P, st) : bf::dispatch<true, true, false>(P, st);
-    return ex ? bf::dispatch<true, false, true>(P, st) : bf::dispatch<true, false, false>(P, st);
-  }
-  if (i8) return ex ? bf::dispatch<false, true, true>(P, st) : bf::dispatch<false, true, false>(P, st);
-  return ex ? bf::dispatch<false, false, true>(P, st) : bf::dispatch<false, false, false>(P, st);
+  const bf::FusedPlan plan = bf::plan_fused({B, C, T, A, M, delay_channels, gains != nullptr, flags, out_scale,
+                                             P.table_bytes, bf::cu_count()});
+  BF_REQUIRE(plan.status == BF_OK, "%s", plan.error);
+  return bf::launch_fused(plan, P, bf::as_stream(stream));
 }
 
 extern "C" double bf_fused_algorithmic_bytes(int B, int C, int T, int A, int M, int delay_channels, int out_int8) {

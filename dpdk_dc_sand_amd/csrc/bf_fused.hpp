@@ -2,6 +2,9 @@
 // bf_wide.hip: the wide kernel for many antennas x beams).
 #pragma once
 
+#include <type_traits>
+
+#include "bf_fused_plan.hpp"
 #include "bf_mfma.hpp"
 #include "bf_phase.hpp"
 
@@ -71,14 +74,6 @@ __device__ __forceinline__ uint32_t requant_bits(int y, float s) {
   return __float_as_uint(__builtin_amdgcn_fmed3f(v, kMagic - 127.0f, kMagic + 127.0f));
 }
 
-// Whether s is a power of two (a normal float with an all-zero mantissa): requant_bits<true> is then exact.
-inline bool scale_is_pow2(float s) {
-  uint32_t u;
-  memcpy(&u, &s, 4);
-  const uint32_t e = (u >> 23) & 255;
-  return (u & 0x7fffffu) == 0 && e > 0 && e < 255;
-}
-
 // [a.b0, b.b0, c.b0, d.b0]: three v_perm_b32
 __device__ __forceinline__ uint32_t pack_low_bytes(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   const uint32_t ab = __builtin_amdgcn_perm(b, a, 0x0c0c0400u);
@@ -109,31 +104,33 @@ __device__ __forceinline__ void lds_barrier() {
   __atomic_signal_fence(__ATOMIC_SEQ_CST);
 }
 
-// Kernel-path override of a launch (flags & BF_FUSED_PATH_MASK): 0 automatic, else one of the BF_FUSED_PATH_* values.
-inline int fused_kernel_choice(const FusedArgs& P) { return P.path; }
-
 // Q14 coefficient tables (bf_q14table.hip): (B, C, M, A) words, or the 32-beam int8 kernel's item layout.
 // kLayoutW32H (a halved limb image) has no generator any more: launch_q14_table refuses it.
 constexpr int kLayoutNatural = 0, kLayoutW32 = 1, kLayoutW32H = 2;
-// k-steps of 32 antennas of the 32-beam int8 kernel, padded to a multiple of 4 (its four-buffer rotation)
-__host__ __device__ inline int w32_table_steps(int A) { return 4 * ((((A + 31) >> 5) + 3) / 4); }
-// The table-driven 32-beam kernel stages at most 4 units of 8 words per thread: Sp <= 8 (A <= 256).
-__host__ __device__ inline bool w32_table_fits(int A) { return w32_table_steps(A) <= 8; }
-// Bytes of the int8 wide path's coefficient table of one launch (kLayoutW32): 1024 Sp words per (b, c, 32-beam slab).
-inline size_t w32_table_bytes(int B, int C, int A, int M) {
-  return static_cast<size_t>(B) * C * ((M + 31) / 32) * 1024 * w32_table_steps(A) * 4;
-}
 int launch_q14_table(const FusedArgs& P, uint32_t* out, int layout, hipStream_t st);
 
-// Integer wide kernels: int8 beams for many antennas x beams.  bf_wide_i8.hip: a workgroup per 32-beam slab
-// (BF_FUSED_PATH_WIDE, and the automatic path beyond the item kernel's shapes).
-bool i8_w32_fits(const FusedArgs& P);
-template <bool Signed>
-int launch_i8_w32(FusedArgs P, hipStream_t st);
+// ---- launching a plan (bf_fused_plan.hpp).  No shape is judged here: each file maps the plan's variant fields to
+// the instantiation of its kernel families, and launch_planned starts it with the plan's configuration.
+using FusedKernel = void (*)(FusedArgs);
 
-// Wide kernel (bf_wide.hip): returns BF_ERR_ARG without launching when the shape does not fit it.
-bool wide_fits(const FusedArgs& P);
-template <bool Signed, bool Exact>
-int launch_wide(FusedArgs P, hipStream_t st);
+// f(std::bool_constant<bs>...): run-time booleans as template arguments.  hipcc emits kernels in the order in which
+// they are instantiated: here lexicographic in the booleans, true first, and in a function body in source order.  No
+// return type on this path is deduced (a deduced one is instantiated at once, ahead of its turn), so the launchers
+// control that order, and keep it as it has always been: device code of two revisions can be compared as text.
+template <class F>
+FusedKernel with_bools(F f) {
+  return f();
+}
+template <class F, class... Bs>
+FusedKernel with_bools(F f, bool b, Bs... bs) {
+  return b ? with_bools([&](auto... cs) -> FusedKernel { return f(std::true_type{}, cs...); }, bs...)
+           : with_bools([&](auto... cs) -> FusedKernel { return f(std::false_type{}, cs...); }, bs...);
+}
+
+// Copies the plan's nslabs, xcd_order and ch_run into P, launches k with the plan's grid, block and LDS, and records
+// the plan's name for bf_last_kernel.
+int launch_planned(FusedKernel k, const FusedPlan& p, FusedArgs P, hipStream_t st);
+int launch_wide(const FusedPlan& p, FusedArgs P, hipStream_t st);  // bf_wide.hip: Wide, WideP2
+int launch_w32(const FusedPlan& p, FusedArgs P, hipStream_t st);   // bf_wide_i8.hip: W32, W32T, W32R
 
 }  // namespace bf

@@ -292,10 +292,3 @@ extern "C" double bf_incoherent_algorithmic_bytes(int B, int C, int T, int A, in
   const double samples = static_cast<double>(B) * C * T;
   return 4.0 * samples * A + (masked ? A : 0) + 4.0 * ((flags & BF_INCOH_SUM_POLS) ? 1 : 2) * (samples / tint);
 }
-
-extern "C" int bf_has_feature(const char* name) {
-  return name && (std::strcmp(name, "incoherent_beam") == 0 || std::strcmp(name, "beam_detect") == 0 ||
-                  std::strcmp(name, "voltage_stats") == 0 || std::strcmp(name, "last_kernel") == 0)
-             ? 1
-             : 0;
-}

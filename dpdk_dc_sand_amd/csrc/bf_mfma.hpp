@@ -4,6 +4,7 @@
 #pragma once
 
 #include "bf_common.hpp"
+#include "bf_fused_dims.hpp"
 
 namespace bf {
 
@@ -103,9 +104,5 @@ __device__ __forceinline__ void store_i8(int8_t* orow, int col0, int M2, const f
       if (col0 + i < M2) orow[col0 + i] = qs[i];
   }
 }
-
-constexpr size_t kMaxLds = 160 * 1024;
-
-inline size_t coef_lds_bytes(int S, int nts) { return static_cast<size_t>(S) * nts * 2 * 64 * 16; }
 
 }  // namespace bf

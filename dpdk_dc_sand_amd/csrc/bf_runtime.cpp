@@ -99,6 +99,12 @@ const char* bf_last_kernel(void) { return bf::g_last_kernel.c_str(); }
 // bf_comm_load and bf_checksum added; the root's own scatter slice is a 2-D copy at N > 1 (include/bf.h).
 int bf_abi_version(void) { return 302; }
 
+int bf_has_feature(const char* name) {
+  for (const char* f : {"incoherent_beam", "beam_detect", "voltage_stats", "last_kernel", "fused_plan"})
+    if (name && std::strcmp(name, f) == 0) return 1;
+  return 0;
+}
+
 int bf_device_count(int* count) {
   BF_REQUIRE(count != nullptr, "bf_device_count: null pointer");
   *count = 0;

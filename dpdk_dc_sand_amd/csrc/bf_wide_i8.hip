@@ -32,15 +32,9 @@ __host__ __device__ inline int w8_padded_steps(int A) { return 2 * ((((A + 31) >
 // two workgroups per CU) and a wave 32 samples x 32 beams: half the voltage bytes per MFMA (each lane loads
 // 8-byte runs = 2 samples of 8 antennas), four step buffers of 16 registers (three steps in flight while one is
 // contracted), and the prefetch runs on across the wave's chunks so the next chunk's steps load under the stores.
-constexpr int kW32Beams = 32;
 
 // k-steps of 32 antennas padded to a multiple of 4 (the four-buffer rotation); padded steps have zero table rows
 __host__ __device__ inline int w32_steps(int A) { return w32_table_steps(A); }
-// LDS: the Q14 limb image (Sp steps x 4 tiles x 2 limbs x 64 lanes x 16 B) + the unsigned correction's partial
-// column sums (4 waves x 64 columns)
-__host__ __device__ inline size_t w32_lds_bytes(int A) {
-  return static_cast<size_t>(w32_steps(A)) * 4 * 2 * 64 * 16 + 4 * 64 * 4;
-}
 
 typedef uint16_t u16x2_t __attribute__((ext_vector_type(2)));
 
@@ -368,7 +362,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32_kernel(Fu
 // from one channel into the next, so only a workgroup's first channel starts cold (measured on the one-channel form: a cold start -- table +
 // first voltage steps -- per (channel, slab) cost ~50 us of 430 at config 4 in a round-3 ablation whose record was
 // not kept).
-constexpr int kW32TChannels = 4;
 
 // Early: request the next channel's table during the last pass's pol-1 stores (else after the last pass).
 // kSp, kNP: compile-time k-steps and passes (config 4: 8 and 2; 0 = from the shape).  With both known, the channel's
@@ -640,7 +633,6 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32t_kernel(F
 //         16 (i & 7) of the wave's 128-byte sample run).
 // Shape: int8 voltages, 8 k-steps (224 < A <= 256), T = 256 (2 passes of 8 straight-line steps), M % 32 == 0,
 // in-workgroup voltage offsets and the beams below 2^31 bytes; 8 channels per workgroup.
-constexpr int kW32RChannels = 8;
 __shared__ __attribute__((aligned(16))) int4 w32r_img[8 * 2 * 2 * 64];  // [step][tile][limb][lane] x 16 B
 __shared__ __attribute__((aligned(16))) int4 w32r_slot0[4 * 256];       // [wave][4 KiB]: even steps
 __shared__ __attribute__((aligned(16))) int4 w32r_slot1[4 * 256];       // odd steps
@@ -912,107 +904,36 @@ __global__ __launch_bounds__(kW8Threads, 2) void beamform_fused_i8_w32r_kernel(F
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// Plan -> instantiation.  W32R: the LDS-DMA ring (int8 voltages).  W32T: config 4's shape takes the straight-line
+// ring, two step buffers (one step in flight while one is contracted: 377 vs 384 us for three buffers and 403 for the
+// runtime loop, profiles/r3_ab_*, r3_g_*) and 8 channels per workgroup (385.5 vs 389.4 us for 4, profiles/r3_ad*);
+// the general form loads through a buffer resource, or through pointers past 2^31.  W32: phasors in the kernel.
 template <bool Signed>
-int launch_w32t_contract(FusedArgs P, hipStream_t st);
-
-// The LDS-DMA ring contraction's shape (beamform_fused_i8_w32r_kernel): 8 k-steps, T = 256, whole 32-beam slabs,
-// every in-workgroup voltage offset and every beam offset below 2^31, a whole launch (no channel chunk).
-bool w32r_fits(const FusedArgs& P) {
-  return w32_steps(P.A) == 8 && P.A > 224 && P.T == 256 && P.M % kW32Beams == 0 && P.c_count == 0 &&
-         static_cast<unsigned long long>(P.A) * P.C * P.T * 4 < (1ull << 31) &&
-         static_cast<unsigned long long>(P.B) * 2 * P.C * P.T * 2 * P.M < (1ull << 31);
-}
-
-// The LDS-DMA ring contraction of one launch whose kLayoutW32 table is ready in P.table on `st` (int8 voltages).
-// Pow2: the output scale is a power of two (requant_bits<true>).
-template <bool Pow2>
-int launch_w32r_contract(FusedArgs P, hipStream_t st) {
-  const long long groups = static_cast<long long>(P.B) * ((P.C + kW32RChannels - 1) / kW32RChannels);
-  const long long grid = P.xcd_order ? (groups + 7) / 8 * 8 * P.nslabs : groups * P.nslabs;
-  BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-  hipLaunchKernelGGL((beamform_fused_i8_w32r_kernel<Pow2>), dim3(static_cast<unsigned>(grid)), dim3(kW8Threads), 0,
-                     st, P);
-  BF_LAUNCHED_TAG("beamform_fused_i8_w32r_kernel", "%s", Pow2 ? "pow2" : "anyscale");
-}
-
-template <bool Signed>
-int launch_w32(FusedArgs P, hipStream_t st) {
-  const size_t lds = w32_lds_bytes(P.A);
-  BF_REQUIRE(lds <= kMaxLds, "bf_beamform_fused: n_ants=%d too large for the integer wide kernel", P.A);
-  P.nslabs = (P.M + kW32Beams - 1) / kW32Beams;
-  P.xcd_order = P.nslabs > 1 && P.order != BF_FUSED_ORDER_CHANNEL;
-  const long long items = static_cast<long long>(P.B) * P.C;
-  const long long grid = P.xcd_order ? (items + 7) / 8 * 8 * P.nslabs : items * P.nslabs;
-  BF_REQUIRE(grid < (1LL << 31), "bf_beamform_fused: grid too large");
-  if (P.table && w32_table_fits(P.A) && P.table_bytes >= w32_table_bytes(P.B, P.C, P.A, P.M)) {
-    // the coefficient table of this launch, written by q14_table_kernel just before on `st`
-    const int e = launch_q14_table(P, const_cast<uint32_t*>(P.table), kLayoutW32, st);
-    if (e != BF_OK) return e;
-    if constexpr (Signed)
-      if (w32r_fits(P))  // config 4's shape: the LDS-DMA voltage ring
-        return scale_is_pow2(P.out_scale * 0x1p-14f) ? launch_w32r_contract<true>(P, st)
-                                                     : launch_w32r_contract<false>(P, st);
-    return launch_w32t_contract<Signed>(P, st);
+FusedKernel w32_kernel(const FusedPlan& p) {
+  if constexpr (Signed)
+    if (p.family == FusedFamily::W32R)
+      return with_bools([](auto pow2) -> FusedKernel { return beamform_fused_i8_w32r_kernel<pow2.value>; }, p.pow2);
+  if (p.family == FusedFamily::W32T) {
+    if (p.straight)
+      return with_bools([](auto pow2) -> FusedKernel {
+        return beamform_fused_i8_w32t_kernel<Signed, false, 8, 2, 2, 8, true, pow2.value>;
+      }, p.pow2);
+    return with_bools([](auto buf) -> FusedKernel {
+      return beamform_fused_i8_w32t_kernel<Signed, false, 0, 0, 4, kW32TChannels, buf.value, false>;
+    }, p.buf);
   }
-  if (P.gain)
-    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, true>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kW8Threads), lds, st, P);
-  else
-    hipLaunchKernelGGL((beamform_fused_i8_w32_kernel<Signed, false>), dim3(static_cast<unsigned>(grid)),
-                       dim3(kW8Threads), lds, st, P);
-  BF_LAUNCHED_TAG("beamform_fused_i8_w32_kernel", "%s", P.gain ? "gain" : "unit");
-}
-
-// The table-driven contraction of one launch (or channel chunk: P.c_count, pointers offset by the caller) whose
-// kLayoutW32 table is ready in P.table on `st`.
-template <bool Signed>
-int launch_w32t_contract(FusedArgs P, hipStream_t st) {
-  const size_t lds = w32_lds_bytes(P.A);
-  {
-    const int Cn = P.c_count ? P.c_count : P.C;
-    const int npasses = ((((P.T >> 1) + 15) >> 4) + 3) >> 2;
-    // config 4's shape walks 8 channels per workgroup (385.5 vs 389.4 us for 4, profiles/r3_ad*), the others 4
-    const bool straight = w32_steps(P.A) == 8 && npasses == 2;
-    const int ch = straight ? 8 : kW32TChannels;
-    const long long groups = static_cast<long long>(P.B) * ((Cn + ch - 1) / ch);
-    const long long tgrid = P.xcd_order ? (groups + 7) / 8 * 8 * P.nslabs : groups * P.nslabs;
-    // buffer-resource voltage loads (no per-load VALU addressing) while every in-workgroup offset is below 2^31
-    const bool buf = static_cast<unsigned long long>(P.A) * P.C * P.T * 4 < (1ull << 31);
-    // a power-of-two scale: the requantisation's multiply and magic add as one exact FMA
-    const bool pow2 = scale_is_pow2(P.out_scale * 0x1p-14f);
-    const dim3 grid3(static_cast<unsigned>(tgrid)), block(kW8Threads);
-    // config 4's shape: the straight-line ring, two step buffers (one step in flight while one is contracted):
-    // 377 vs 384 us for three buffers and 403 for the runtime loop (profiles/r3_ab_*, r3_g_*)
-    if (straight && buf && pow2)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 8, 2, 2, 8, true, true>), grid3, block,
-                         lds, st, P);
-    else if (straight && buf)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 8, 2, 2, 8, true, false>), grid3, block,
-                         lds, st, P);
-    else if (buf)
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false, 0, 0, 4, kW32TChannels, true, false>),
-                         grid3, block, lds, st, P);
-    else  // offsets past 2^31 (A C T 4 >= 2 GiB): the pointer form
-      hipLaunchKernelGGL((beamform_fused_i8_w32t_kernel<Signed, false>), grid3, block, lds, st, P);
-    BF_LAUNCHED_TAG("beamform_fused_i8_w32t_kernel", "%s",
-                    straight && buf ? (pow2 ? "straight,pow2" : "straight,anyscale") : buf ? "general,buf" : "general,ptr");
-  }
+  return with_bools([](auto gain) -> FusedKernel { return beamform_fused_i8_w32_kernel<Signed, gain.value>; }, p.gain);
 }
 
 }  // namespace
 
-bool i8_w32_fits(const FusedArgs& P) {
-  const size_t ant_stride = static_cast<size_t>(P.C) * P.T * 4;
-  return P.A >= 32 && (P.T & 1) == 0 && 24 * ant_stride + static_cast<size_t>(P.T) * 4 < (1ull << 32) &&
-         w32_lds_bytes(P.A) <= kMaxLds;
+int launch_w32(const FusedPlan& p, FusedArgs P, hipStream_t st) {
+  if (p.table) {
+    // the coefficient table of this launch, written by q14_table_kernel just before on `st`
+    const int e = launch_q14_table(P, const_cast<uint32_t*>(P.table), kLayoutW32, st);
+    if (e != BF_OK) return e;
+  }
+  return launch_planned(!p.sgn ? w32_kernel<false>(p) : w32_kernel<true>(p), p, P, st);
 }
-
-template <bool Signed>
-int launch_i8_w32(FusedArgs P, hipStream_t st) {
-  return launch_w32<Signed>(P, st);
-}
-
-template int launch_i8_w32<false>(FusedArgs, hipStream_t);
-template int launch_i8_w32<true>(FusedArgs, hipStream_t);
 
 }  // namespace bf

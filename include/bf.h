@@ -39,10 +39,10 @@ const char* bf_last_error(void);
  * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
- * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel. */
+ * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan. */
 int bf_abi_version(void);
-/* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel"), 0 for
- * any other name (and for NULL). */
+/* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
+ * "fused_plan"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -224,6 +224,27 @@ int bf_beamform_fused_ws(const uint8_t* raw, const float* delay_vals, int delay_
                          int B, int C, int T, int A, int M, int Ctot, int xeng_id, double sample_period, double t0,
                          double batch_dt, int flags, float out_scale, void* workspace, size_t workspace_bytes,
                          void* stream);
+
+/* The launch bf_beamform_fused_ws would make for a call, as a pure host function (no device, no launch; like
+ * bf_scatter_plan): which kernel a shape takes is decided in one place, and this asks it.  The arguments are the
+ * call's: has_gains = gains != NULL, workspace_bytes = what the call would offer (0: none), cus = the device's compute
+ * units (sizes the persistent kernel's grid only; 0 = the current device's, 256 when there is none).  T must be a
+ * multiple of 16, delay_channels 1 or C.
+ *   kernel          : the name bf_last_kernel reports after the call
+ *   uses_table      : 1 when the Q14 table is generated into the workspace first (bf_q14_coeffs' kernel)
+ *   workspace_bytes : what the table occupies there (0 without); bf_fused_workspace_bytes is this value for an
+ *                     unlimited workspace
+ *   grid, block, lds_bytes, nslabs, xcd_order, ch_run : the launch configuration of the contraction kernel
+ * A call that bf_beamform_fused_ws would refuse for its shape (too many antennas for any kernel's LDS, a grid beyond
+ * 2^31, the int32 bound of the Q14 contract) returns BF_ERR_ARG with the same message in bf_last_error. */
+typedef struct bf_fused_plan_info {
+  char kernel[96];
+  int uses_table, nslabs, xcd_order, ch_run;
+  unsigned grid, block;
+  size_t lds_bytes, workspace_bytes;
+} bf_fused_plan_info;
+int bf_fused_plan(int B, int C, int T, int A, int M, int delay_channels, int has_gains, int flags, float out_scale,
+                  size_t workspace_bytes, int cus, bf_fused_plan_info* out);
 
 /* The int8 path's steering coefficients (the Q14 integer contract, oracle quantise_coeffs of fused_tables):
  *   out[b][c][m][a] = (uint16)Wc | (uint32)Ws << 16, Wc = rne(2^14 * RN32(g * RN32(cos rot))), Ws the same for sin,

@@ -3,15 +3,18 @@
 Each case places every device buffer at its minimum legal alignment between two 64 KiB guards, launches twice over
 different fills, and demands: identical output bits in both runs, the case's oracle met, guards and inputs untouched,
 and -- through bf_last_kernel -- that the kernel variant the case claims to cover is the one that ran.  The expected
-names are written out per case (read from the dispatch code in csrc/); where a name disagrees, the shape is what is
-wrong.  Shapes are the smallest that reach a variant.  The >= 2 GiB pointer-form variants (wide `ptr`, w32t
-`general,ptr`) belong to tests/test_gpu_fullsize.py."""
+names are written out per case; where a name disagrees, the shape is what is wrong.  The fused cases live in
+tests/fused_cases.py: tests/test_fused_plan_host.py holds the host-side launch plan (bf_fused_plan) to the same names
+without a GPU, and every fused call here checks that the plan named the kernel that ran.  Shapes are the smallest that
+reach a variant.  The >= 2 GiB pointer-form variants (wide `ptr`, w32t `general,ptr`) belong to
+tests/test_gpu_fullsize.py."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import detect_ref
+import fused_cases as FC
 import guarded as gd
 import incoherent_ref
 import oracle as O
@@ -23,9 +26,7 @@ pytestmark = pytest.mark.gpu
 TS = O.TS_MEERKAT
 CTOT, XENG, T0 = 8192, 3, 2.5e-3
 BDT = 256 * 8192 * TS
-SIGNED, OUT_I8, EXACT, VIA_F32 = _lib.FUSED_SIGNED, _lib.FUSED_OUT_INT8, _lib.FUSED_EXACT_COEFF, _lib.FUSED_INT8_VIA_F32
-PATH, ORDER = _lib.FUSED_PATH, _lib.FUSED_ORDER
-S6 = float(np.float32(1 / 6))  # a scale that is no power of two
+SIGNED, OUT_I8, VIA_F32, S6 = FC.SIGNED, FC.OUT_I8, FC.VIA_F32, FC.S6
 
 
 @pytest.fixture(scope="module")
@@ -59,21 +60,20 @@ def unit_gains(M, A, seed):
     return np.random.default_rng(seed).uniform(0.25, 1.0, (M, A)).astype(np.float32)
 
 
-def fused(ex, A, M, T, B, C, flags, expect, dch=1, gains=None, scale=1.0, workspace=False, amp=None, f32_of=None):
-    """One guarded bf_beamform_fused_ws call against the oracle of its contract.  Returns the beams."""
+def fused(ex, c, f32_of=None):
+    """One guarded bf_beamform_fused_ws call (a fused_cases.Call) against the oracle of its contract.  Returns the beams."""
+    A, M, T, B, C, flags, dch, scale = c.A, c.M, c.T, c.B, c.C, c.flags, c.dch, c.scale
     signed, i8 = bool(flags & SIGNED), bool(flags & OUT_I8)
-    raw = voltages((B, A, C, T, 2, 2), signed, A * 131 + M * 7 + T + C, amp)
+    raw = voltages((B, A, C, T, 2, 2), signed, A * 131 + M * 7 + T + C, c.amp)
     d = delays(dch, M, A, A * 31 + M)
+    gains = None if c.gains is None else unit_gains(M, A, c.gains)
     rawv = raw.view(np.int8) if signed else raw
     bufs = [gd.inp("raw", raw, 16), gd.inp("dv", d, 16),
             gd.out("y", (B, 2, C, T // 16, 16, 2 * M), np.int8 if i8 else np.float32, 16)]
     if gains is not None:
         bufs.append(gd.inp("gains", gains, 4))
-    ws_bytes = 0
-    if workspace:
-        n = ctypes.c_size_t(0)
-        _lib.call("bf_fused_workspace_bytes", B, C, T, A, M, flags, ctypes.byref(n))
-        ws_bytes = n.value
+    ws_bytes = FC.workspace_bytes(c)
+    if c.workspace:
         assert ws_bytes > 0, "the case expects a shape that uses the workspace"
         bufs.append(gd.out("ws", (ws_bytes,), np.uint8, 16))
 
@@ -95,49 +95,37 @@ def fused(ex, A, M, T, B, C, flags, expect, dch=1, gains=None, scale=1.0, worksp
             w = O.fused_tables(d, B, C, CTOT, A, xeng_id=XENG, t0=T0, batch_dt=BDT, gains=gains)
             assert_beams_allclose(y, ref, O.reorder(rawv), w, signed=signed)
 
-    return gd.run_case(ex, bufs, launch, oracle, expect)["y"]
+    y = gd.run_case(ex, bufs, launch, oracle, c.expect)["y"]
+    assert FC.planned_name(c) == _lib.load().bf_last_kernel().decode()  # the plan, asked on the host, is what ran
+    return y
 
 
-# ---- bf_beamform_fused_ws, float beams ---------------------------------------------------------------------------------
-ITEM, GEN, WIDE = "beamform_fused_item_kernel:f32,", "beamform_fused_kernel:f32,", "beamform_fused_wide_kernel:"
-F32_CASES = [  # (A, M, T), path, expected name ({e} = exact | fast)
-    ((19, 16, 48), "auto", ITEM + "nts2,full,{e},staged"), ((64, 16, 256), "auto", ITEM + "nts2,full,{e},staged"),
-    ((40, 32, 64), "auto", ITEM + "nts2,full,{e}"),
-    ((33, 9, 80), "auto", ITEM + "nts2,partial,{e}"), ((48, 24, 32), "auto", ITEM + "nts2,partial,{e}"),
-    ((16, 8, 48), "auto", ITEM + "nts1,full,{e}"),
-    ((5, 3, 16), "auto", ITEM + "nts1,partial,{e}"), ((64, 1, 256), "auto", ITEM + "nts1,partial,{e}"),
-    ((130, 9, 64), "auto", GEN + "nts2,{e}"),
-    ((80, 2, 16), "auto", GEN + "nts1,{e}"), ((4, 1, 272), "auto", GEN + "nts1,{e}"),
-    ((16, 3, 32), "wide", WIDE + "tw1,{e},unit,buf"), ((656, 20, 32), "wide", WIDE + "tw1,{e},unit,buf"),
-]
+def run(ex, calls):
+    """The calls of one case in order; a call that requantises gets the previous call's float beams as its oracle."""
+    y = None
+    for c in calls:
+        y = fused(ex, c, f32_of=y if c.requant_of_previous else None)
 
 
-@pytest.mark.parametrize("shape,path,expect", F32_CASES, ids=[f"{s[0]}x{s[1]}x{s[2]}" for s, _, _ in F32_CASES])
+# ---- bf_beamform_fused_ws: the cases and their expected names are tests/fused_cases.py -------------------------------
+@pytest.mark.parametrize("case", FC.F32_CASES, ids=[f"{s[0]}x{s[1]}x{s[2]}" for s, _, _ in FC.F32_CASES])
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
 @pytest.mark.parametrize("exact", [False, True], ids=["fast", "exact"])
-def test_fused_f32(ex, shape, path, expect, signed, exact):
-    A, M, T = shape
-    flags = (SIGNED if signed else 0) | (EXACT if exact else 0) | PATH[path]
-    fused(ex, A, M, T, 2, 3, flags, expect.format(e="exact" if exact else "fast"), dch=1 if A % 2 else 3)
+def test_fused_f32(ex, case, signed, exact):
+    run(ex, FC.f32(case, signed, exact))
 
 
-@pytest.mark.parametrize("shape", [(72, 33, 64), (200, 40, 96)], ids=str)
+@pytest.mark.parametrize("shape", FC.F32_WIDE_SHAPES, ids=str)
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
 @pytest.mark.parametrize("exact", [False, True], ids=["fast", "exact"])
 @pytest.mark.parametrize("weighted", [False, True], ids=["unit", "gain"])
 def test_fused_f32_wide_32_beam_slabs(ex, shape, signed, exact, weighted):
     """Per-channel delay models (delay_channels = C), a pulled-back last k-step, a partial last slab."""
-    A, M, T = shape
-    flags = (SIGNED if signed else 0) | (EXACT if exact else 0)
-    g = unit_gains(M, A, A) if weighted else None
-    name = f"{WIDE}tw2,{'exact' if exact else 'fast'},{'gain' if weighted else 'unit'},buf"
-    fused(ex, A, M, T, 2, 3, flags, name, dch=3, gains=g)
+    run(ex, FC.f32_wide_32_beam_slabs(shape, signed, exact, weighted))
 
 
 def test_fused_f32_item_kernel_with_gains(ex):
-    fused(ex, 33, 9, 80, 2, 3, SIGNED, ITEM + "nts2,partial,fast", gains=unit_gains(9, 33, 1))
-    fused(ex, 656, 20, 32, 1, 2, PATH["wide"], WIDE + "tw1,fast,gain,buf", gains=unit_gains(20, 656, 2))
-    fused(ex, 16, 3, 32, 2, 3, PATH["wide"] | EXACT, WIDE + "tw1,exact,gain,buf", gains=unit_gains(3, 16, 3))
+    run(ex, FC.f32_item_kernel_with_gains())
 
 
 @pytest.mark.parametrize("C", [2, 3])
@@ -145,86 +133,47 @@ def test_fused_f32_item_kernel_with_gains(ex):
 def test_fused_f32_persistent_wide_p2_and_its_refusal(ex, C, signed):
     """Config 4's item shape takes the persistent kernel; BF_FUSED_ORDER_CHANNEL, which it cannot honour, must take
     the slab kernel, and so must exact coefficients."""
-    s = SIGNED if signed else 0
-    fused(ex, 256, 32, 256, 1, C, s, "beamform_fused_wide_p2_kernel")
-    fused(ex, 256, 32, 256, 1, C, s | ORDER["channel"], WIDE + "tw2,fast,unit,buf")
-    if C == 2:
-        fused(ex, 256, 32, 256, 1, C, s | EXACT, WIDE + "tw2,exact,unit,buf")
-
-
-# ---- bf_beamform_fused_ws, int8 beams, the Q14 integer contract ------------------------------------------------------
-I8ITEM = "beamform_fused_i8_item_kernel:"
-I8_FORM = {1: "nts1,partial", 8: "nts1,full", 12: "nts2,partial", 16: "nts2,full"}
+    run(ex, FC.f32_persistent_wide_p2_and_its_refusal(C, signed))
 
 
 @pytest.mark.parametrize("M", [1, 8, 12, 16])
 @pytest.mark.parametrize("A", [64, 61])
-@pytest.mark.parametrize("scale", [1 / 64, S6], ids=["pow2", "sixth"])
+@pytest.mark.parametrize("scale", FC.I8_ITEM_SCALES, ids=["pow2", "sixth"])
 def test_fused_i8_item_kernel(ex, M, A, scale):
     """Every (nts, full) form x (a64, pow2) form; T and the sample type cycle through 16 / 144 / 256, int8 / uint8."""
-    k = [1, 8, 12, 16].index(M) + (A == 61) + 2 * (scale != 1 / 64)
-    T, signed = (16, 144, 256)[k % 3], k % 2 == 0
-    name = f"{I8ITEM}{I8_FORM[M]},{'a64' if A == 64 else 'aany'},{'pow2' if scale == 1 / 64 else 'anyscale'}"
-    fused(ex, A, M, T, 2, 3, OUT_I8 | (SIGNED if signed else 0), name, scale=scale, amp=None if scale == 1 / 64 else 6)
+    run(ex, FC.i8_item_kernel(M, A, scale))
 
 
-@pytest.mark.parametrize("shape,name", [((130, 9, 64), "nts2"), ((19, 3, 48), "nts1")], ids=str)
+@pytest.mark.parametrize("case", FC.I8_GENERIC_CASES, ids=[str(s) + "-" + n for s, n in FC.I8_GENERIC_CASES])
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
-def test_fused_i8_generic_kernel(ex, shape, name, signed):
-    A, M, T = shape
-    fused(ex, A, M, T, 2, 3, OUT_I8 | (SIGNED if signed else 0) | PATH["generic"], "beamform_fused_i8_kernel:" + name,
-          scale=1 / 64, dch=3)
+def test_fused_i8_generic_kernel(ex, case, signed):
+    run(ex, FC.i8_generic_kernel(case, signed))
 
 
-@pytest.mark.parametrize("shape", [(40, 32, 64), (72, 33, 64), (200, 40, 96)], ids=str)
+@pytest.mark.parametrize("shape", FC.I8_W32_SHAPES, ids=str)
 @pytest.mark.parametrize("signed", [False, True], ids=["u8", "s8"])
 @pytest.mark.parametrize("weighted", [False, True], ids=["unit", "gain"])
 def test_fused_i8_w32_in_kernel_phasors(ex, shape, signed, weighted):
     """No workspace: the 32-beam integer kernel evaluates its phasors itself.  (72, 33): byte stores, a partial slab."""
-    A, M, T = shape
-    g = unit_gains(M, A, M) if weighted else None
-    fused(ex, A, M, T, 2, 3, OUT_I8 | (SIGNED if signed else 0) | PATH["wide"],
-          "beamform_fused_i8_w32_kernel:" + ("gain" if weighted else "unit"), scale=1 / 128, gains=g, dch=3)
-
-
-W32T, W32R = "beamform_fused_i8_w32t_kernel:", "beamform_fused_i8_w32r_kernel:"
+    run(ex, FC.i8_w32_in_kernel_phasors(shape, signed, weighted))
 
 
 @pytest.mark.parametrize("weighted", [False, True], ids=["unit", "gain"])
-@pytest.mark.parametrize("A,M,T,B,C,signed,scale,name", [
-    (64, 40, 64, 2, 3, False, 1 / 64, W32T + "general,buf"), (64, 40, 64, 2, 3, True, S6 / 8, W32T + "general,buf"),
-    (256, 64, 256, 1, 2, False, 1 / 256, W32T + "straight,pow2"),
-    (256, 64, 256, 1, 2, False, S6 / 32, W32T + "straight,anyscale"),
-    (256, 40, 256, 1, 2, True, 1 / 128, W32T + "straight,pow2"),
-    (256, 40, 256, 1, 2, True, S6 / 16, W32T + "straight,anyscale"),
-    (256, 32, 256, 1, 2, True, 1 / 128, W32R + "pow2"), (256, 32, 256, 1, 5, True, 1 / 128, W32R + "pow2"),
-    (256, 32, 256, 1, 2, True, S6 / 16, W32R + "anyscale"), (256, 32, 256, 1, 5, True, S6 / 16, W32R + "anyscale")])
-def test_fused_i8_with_guarded_workspace(ex, A, M, T, B, C, signed, scale, name, weighted):
+@pytest.mark.parametrize("case", FC.I8_WORKSPACE_CASES, ids=["-".join(map(str, c)) for c in FC.I8_WORKSPACE_CASES])
+def test_fused_i8_with_guarded_workspace(ex, case, weighted):
     """A workspace of exactly bf_fused_workspace_bytes, guarded as an output: the generated Q14 table (the generator's
     item layout, with and without gains) is written wholly inside it.  C = 5 is not a multiple of the ring kernel's
     channels per workgroup."""
-    fused(ex, A, M, T, B, C, OUT_I8 | (SIGNED if signed else 0) | PATH["wide"], name, scale=scale, workspace=True,
-          gains=unit_gains(M, A, A + M) if weighted else None)
+    run(ex, FC.i8_with_guarded_workspace(case, weighted))
 
 
-@pytest.mark.parametrize("A,M,T,form", [
-    (64, 16, 256, "item:nts2,full"), (33, 9, 80, "item:nts2,partial"), (16, 8, 48, "item:nts1,full"),
-    (5, 3, 16, "item:nts1,partial"), (130, 9, 64, "generic:nts2"), (80, 2, 16, "generic:nts1")])
-@pytest.mark.parametrize("scale", [1 / 64, S6 / 8], ids=["pow2", "sixth"])
+@pytest.mark.parametrize("case", FC.VIA_F32_CASES, ids=["-".join(map(str, c)) for c in FC.VIA_F32_CASES])
+@pytest.mark.parametrize("scale", FC.VIA_F32_SCALES, ids=["pow2", "sixth"])
 @pytest.mark.parametrize("exact", [False, True], ids=["fast", "exact"])
-def test_fused_i8_via_f32(ex, A, M, T, form, scale, exact):
+def test_fused_i8_via_f32(ex, case, scale, exact):
     """BF_FUSED_INT8_VIA_F32 == bf_requant of the same call's float beams (themselves held to the float tolerance):
     every form of the item kernel's requantising instantiation, and the generic kernel's."""
-    kind, nts = form.split(":")
-    e = "exact" if exact else "fast"
-    flags = SIGNED | (EXACT if exact else 0)
-    if kind == "item":
-        f32_name = f"{ITEM}{nts},{e}" + (",staged" if M == 16 else "")
-        name = f"beamform_fused_item_kernel:i8,{nts},{e},{'pow2' if scale == 1 / 64 else 'anyscale'}"
-    else:
-        f32_name, name = f"{GEN}{nts},{e}", f"beamform_fused_kernel:i8,{nts},{e}"
-    y = fused(ex, A, M, T, 2, 3, flags, f32_name)
-    fused(ex, A, M, T, 2, 3, flags | OUT_I8 | VIA_F32, name, scale=scale, f32_of=y)
+    run(ex, FC.i8_via_f32(case, scale, exact))
 
 
 # ---- bf_beamform --------------------------------------------------------------------------------------------------------
