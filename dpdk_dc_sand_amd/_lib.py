@@ -93,6 +93,8 @@ PROTOTYPES = {
     "bf_voltage_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_float, c_float, c_float, c_void_p]),
     "bf_vstats_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_correlate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "bf_correlate_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -119,6 +121,8 @@ DETECT_IN_INT8, DETECT_STOKES_IQUV = 1, 2
 # bf_voltage_stats flags and the output bit mask of bf_vstats_algorithmic_bytes
 VSTATS_SIGNED = 1
 VSTATS_POWER, VSTATS_SK, VSTATS_FLAGS = 1, 2, 4
+# bf_correlate flags
+CORR_SIGNED, CORR_ACCUMULATE = 1, 2
 
 
 class BeamformerError(RuntimeError):

@@ -13,13 +13,17 @@ with H2D, compute and D2H overlapped), beamforming.incoherent -> IncoherentBeamT
 antenna power sums of the same raw voltages, integrated in time; bit-exact integer contract), beamforming.detect ->
 BeamDetectorTemplate / BeamDetector (Stokes I or IQUV power of the beams, integrated in time and frequency, bound to
 FusedBeamformer.outData), beamforming.vstats -> VoltageStatsTemplate / VoltageStats (per-antenna power, spectral
-kurtosis and RFI flags of the same raw voltages; antenna_mask_from_flags turns the flags into an antenna mask).
+kurtosis and RFI flags of the same raw voltages; antenna_mask_from_flags turns the flags into an antenna mask),
+beamforming.correlate -> CorrelatorTemplate / Correlator (integer visibilities of every antenna pair of the same raw
+voltages; n_baselines, baseline_index and visibility_matrix read the triangular output).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
 from .beamform_op_sequence import OpSequence, OpSequenceTemplate  # noqa: F401
 from .coeff_generator import CoeffGenerator, CoeffGeneratorTemplate  # noqa: F401
 from .complex_mult_kernel import ComplexMultKernel  # noqa: F401
+from .correlate import (Correlator, CorrelatorTemplate, baseline_index, n_baselines,  # noqa: F401
+                        visibility_matrix)
 from .detect import BeamDetector, BeamDetectorTemplate  # noqa: F401
 from .fused import FusedBeamformer, FusedBeamformerTemplate  # noqa: F401
 from .incoherent import IncoherentBeam, IncoherentBeamTemplate  # noqa: F401

@@ -39,10 +39,11 @@ const char* bf_last_error(void);
  * entry points without a new number; bf_has_feature (itself one of them: look it up with dlsym) tells a caller whether
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
- * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan. */
+ * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
+ * bf_correlate and bf_correlate_algorithmic_bytes. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan"), 0 for any other name (and for NULL). */
+ * "fused_plan", "correlate"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -67,6 +68,7 @@ const char* bf_last_kernel(void);
  *   bf_incoherent_beam                raw 16, ant_mask 1 (none), out 4
  *   bf_beam_detect                    beams 16, out 4
  *   bf_voltage_stats                  raw 16, out_power 4, out_sk 4, out_flags 1 (none)
+ *   bf_correlate                      raw 16, out 4
  *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -326,6 +328,33 @@ double bf_detect_algorithmic_bytes(int B, int C, int T, int M, int tint, int fin
 int bf_voltage_stats(const uint8_t* raw, float* out_power, float* out_sk, uint8_t* out_flags, int B, int C, int T,
                      int A, int tint, int flags, float scale, float sk_lo, float sk_hi, void* stream);
 double bf_vstats_algorithmic_bytes(int B, int C, int T, int A, int tint, int outputs);
+
+/* The correlator (no reference counterpart; the X-engine half of the engine the reference belongs to): the integer
+ * visibilities of every antenna pair, from the fused operator's own input cube -- what delay and phase models, beam
+ * weights and dead-antenna decisions are solved from:
+ *   raw : 8-bit (B, A, C, T, 2, 2), uint8, or int8 with BF_CORR_SIGNED (the sample_signed convention)
+ *   out : int32 (B/bint, C, T/tint, NBL, 2, 2, 2), NBL = A (A + 1) / 2; the baseline of (a1, a2), a1 >= a2, has index
+ *         a1 (a1 + 1) / 2 + a2 (autos included); the last three axes are (p1, p2, (re, im))
+ * With x[a,p] = re + i*im of one sample, for the window b in [k*bint, (k+1)*bint), t in [j*tint, (j+1)*tint):
+ *   S[k][c][j][bl(a1,a2)][p1][p2] = sum over the window of x[a1,p1] * conj(x[a2,p2])
+ *      re = sum r1*r2 + i1*i2        im = sum i1*r2 - r1*i2                                       (exact integers)
+ * (x[a,0] = 3+4i, x[a,1] = 1+2i: the auto is (0,0) = 25, (0,1) = 11-2i, (1,0) = 11+2i, (1,1) = 5 per sample).  All
+ * four pol products of an auto are stored: (1,0) is the conjugate of (0,1), redundant, but the layout stays one.
+ * Without BF_CORR_ACCUMULATE every output element is written once by one thread (no atomics: out need not be zeroed);
+ * with it the same thread reads the old value, adds and stores, in uint32 arithmetic (wrap-around is defined), and
+ * keeping the sum of several calls inside int32 is the caller's business.  The input is never written; the result does
+ * not depend on the order of summation.  B, C, A >= 1, A <= 2048; T % 16 == 0, T <= 2^20; tint is a multiple of 16
+ * that divides T; bint >= 1 divides B, and bint > 1 needs tint == T; the samples per window n = bint * tint keep every
+ * sum in int32: n <= 65535 for int8 (|term| <= 2 * 128^2), n <= 16512 for uint8 (term <= 2 * 255^2); unknown flag bits
+ * are refused; raw 16-byte, out 4-byte aligned; a launch beyond 2^31 - 1 workgroups is refused.  Every refusal is
+ * BF_ERR_ARG before any launch.
+ * bf_correlate_algorithmic_bytes: 4*B*A*C*T voltage bytes plus 32 * NBL * (B/bint) * C * (T/tint) output bytes (twice
+ * with BF_CORR_ACCUMULATE: read and written); 0 for any argument bf_correlate would refuse. */
+#define BF_CORR_SIGNED 1       /* int8 samples (the sample_signed convention), else uint8 */
+#define BF_CORR_ACCUMULATE 2   /* out += S instead of out = S */
+int bf_correlate(const uint8_t* raw, int32_t* out, int B, int C, int T, int A, int tint, int bint, int flags,
+                 void* stream);
+double bf_correlate_algorithmic_bytes(int B, int C, int T, int A, int tint, int bint, int flags);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

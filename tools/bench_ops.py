@@ -9,7 +9,10 @@ ceiling for the same read and write bytes (build/libbf_stream.so, `make stream`)
 configuration's shape, (tint, fint) = (16, 1) and (T, 16), Stokes I and IQUV), each line with the stream ceiling in the
 same way; `--detect` runs only these.  `--vstats` runs the voltage statistics alone, at cfg3 and cfg4: integration 256
 and 16, all three outputs and the power alone, each line with the stream ceiling for its own bytes, and the incoherent
-beam on the same cube at the same integration, all in one process.
+beam on the same cube at the same integration, all in one process.  `--correlate` runs the correlator alone, at cfg3
+(integration T over all 8 batches) and cfg4 (integration T), each line with the stream ceiling for its own bytes and the
+useful int8 operation rate (NBL * 4 * 8 operations per channel-sample), then the incoherent beam on the same cube in
+the same process; its lines also go to `--out` (profiles/correlate_ops.jsonl).
 """
 import argparse
 import ctypes
@@ -23,10 +26,10 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from dpdk_dc_sand_amd import accel  # noqa: E402
+from dpdk_dc_sand_amd import _lib, accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, CoeffGeneratorTemplate,  # noqa: E402
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
-                                          PreBeamformReorderTemplate, VoltageStatsTemplate)
+                                          PreBeamformReorderTemplate, VoltageStatsTemplate, CorrelatorTemplate)
 
 TS = 1 / 1712e6
 HBM = 8.0e12
@@ -38,6 +41,8 @@ CONFIGS = {
 }
 INCOHERENT_CONFIGS = ("cfg2", "cfg3", "cfg4")
 VSTATS_CONFIGS = ("cfg3", "cfg4")
+CORRELATE_CONFIGS = {"cfg3": dict(bint=8), "cfg4": dict(bint=1)}  # integration = T
+INT8_MFMA_PEAK = 5.0e15  # dense int8 MFMA operations per second: twice the 2.5 PFLOP/s dense BF16 rate
 
 
 def timeit(queue, fn, reps, settle_s=0.2):
@@ -56,11 +61,17 @@ def timeit(queue, fn, reps, settle_s=0.2):
     return e1.time_since(e0) / reps
 
 
+EMIT_FILE = None  # --correlate: an open file that receives every line as well
+
+
 def emit(cfg, op, seconds, alg_bytes, **extra):
     line = {"config": cfg, "op": op, "us": round(seconds * 1e6, 2), "alg_bytes": int(alg_bytes),
             "achieved_GBps": round(alg_bytes / seconds / 1e9, 1), "frac_8TBps": round(alg_bytes / seconds / HBM, 4)}
     line.update(extra)
     print(json.dumps(line), flush=True)
+    if EMIT_FILE is not None:
+        EMIT_FILE.write(json.dumps(line) + "\n")
+        EMIT_FILE.flush()
 
 
 def delays(C, M, A, rng):
@@ -228,6 +239,37 @@ def run_vstats(ctx, q, name, c, reps, rng):
         measure(f"incoherent_tint{tint}", IncoherentBeamTemplate(ctx, B, C, T, A, integration=tint), ("outData",), tint)
 
 
+def run_correlate(ctx, q, name, c, reps, rng, bint):
+    """The correlator over the configuration's voltage cube, uint8, integration T over `bint` batches, with the stream
+    ceiling for its own read and write bytes and the useful int8 operation rate; then the incoherent beam (integration
+    T, per pol) on the same cube with its own ceiling, in the same process."""
+    A, C, T, B = c["A"], c["C"], c["T"], c["B"]
+    raw = accel.DeviceArray(ctx, (B, A, C, T, 2, 2), np.uint8)
+    raw.set(q, rng.integers(0, 256, raw.shape, dtype=np.uint8))
+
+    def measure(label, tmpl, out_name, **extra):
+        op = tmpl.instantiate(q)
+        op.bind(inSamples=raw)
+        op.ensure_all_bound()
+        t = timeit(q, op, reps)
+        read_bytes, write_bytes = raw.nbytes, op.buffer(out_name).nbytes
+        assert tmpl.algorithmic_bytes() == read_bytes + write_bytes
+        kernel = _lib.load().bf_last_kernel().decode()
+        del op
+        ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+        emit(name, label, t, tmpl.algorithmic_bytes(), integration=T, read_bytes=read_bytes, write_bytes=write_bytes,
+             kernel=kernel, ceiling_us=round(ct * 1e6, 2), ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+             ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4),
+             **{k: (v(t) if callable(v) else v) for k, v in extra.items()})
+
+    ops = (A * (A + 1) // 2) * 4 * 8 * B * C * T  # useful int8 operations: NBL * 4 * 8 per channel-sample
+    measure(f"correlate_tint{T}_bint{bint}", CorrelatorTemplate(ctx, B, C, T, A, integration=T, batch_integration=bint),
+            "outVisibilities", batch_integration=bint, n_baselines=A * (A + 1) // 2, useful_int8_ops=ops,
+            useful_int8_Tops=lambda t: round(ops / t / 1e12, 2),
+            frac_int8_mfma_peak=lambda t: round(ops / t / INT8_MFMA_PEAK, 4))
+    measure(f"incoherent_tint{T}", IncoherentBeamTemplate(ctx, B, C, T, A, integration=T), "outData")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -237,13 +279,22 @@ def main():
     p.add_argument("--detect", action="store_true", help="only the beam detector and its stream ceiling")
     p.add_argument("--vstats", action="store_true", help="only the voltage statistics, their stream ceiling and the "
                    "incoherent beam on the same cube")
+    p.add_argument("--correlate", action="store_true", help="only the correlator, its stream ceiling and the "
+                   "incoherent beam on the same cube")
+    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "correlate_ops.jsonl"),
+                   help="--correlate: the file that receives the lines as well")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
+    if args.correlate:
+        global EMIT_FILE
+        EMIT_FILE = open(args.out, "w")
     for name in args.only.split(","):
-        if args.incoherent or args.detect or args.vstats:
+        if args.incoherent or args.detect or args.vstats or args.correlate:
+            if name in CORRELATE_CONFIGS and args.correlate:
+                run_correlate(ctx, q, name, CONFIGS[name], args.reps, rng, **CORRELATE_CONFIGS[name])
             if name in VSTATS_CONFIGS and args.vstats:
                 run_vstats(ctx, q, name, CONFIGS[name], args.reps, rng)
             if name in INCOHERENT_CONFIGS and args.incoherent:
