@@ -63,6 +63,7 @@ PROTOTYPES = {
     "bf_beamform_fused_weighted": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                            c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_float,
                                            c_void_p]),
+    "bf_check_gains": (c_int, [c_void_p, c_int, c_int, c_int]),
     "bf_fused_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P_size_t]),
     "bf_beamform_fused_ws": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_double, c_double, c_double, c_int, c_float, c_void_p,

@@ -123,17 +123,22 @@ class FusedBeamformerTemplate:
     def check_weights(self, weights):
         """Validate an (M, A) weight table for this configuration; returns it as float32.  The int8 output's
         Q14 integer path needs rne(|g| * 2^14) <= 32639, i.e. |g| <= 1.992 (the high limb stays int8), and
-        A * max|x| * (sqrt(2) * max|g| * 2^14 + 1) < 2^31 (no int32 overflow); the float path takes any finite
-        weights."""
+        A * max|x| * (sqrt(2) * max|g| * 2^14 + 1) < 2^31 (no int32 overflow).  The float path (float beams, and
+        int8_contract="f32") carries each coefficient as an f16 hi/lo pair: |g| <= 65504, beyond which the beams
+        would be inf or NaN, and weights far below 1 lose accuracy relative to their own size (the coefficient
+        domain and floor in include/bf.h, at bf_beamform)."""
         w = np.asarray(weights, np.float32)
         if w.shape != self.weights_shape:
             raise ValueError(f"beam weights must have shape {self.weights_shape}, got {w.shape}")
         if not np.all(np.isfinite(w)):
             raise ValueError("beam weights must be finite")
+        g = float(np.max(np.abs(w))) if w.size else 0.0
         if self.out_int8 and self.int8_contract == "q14":
-            g = float(np.max(np.abs(w))) if w.size else 0.0
             if np.rint(g * 16384) > 32639 or self._int8_sum_bound(self.n_ants, self.sample_signed, g) >= 2 ** 31:
                 raise ValueError(f"beam weight magnitude {g} out of range for int8 output with {self.n_ants} inputs")
+        elif g > 65504.0:
+            raise ValueError(f"beam weight magnitude {g} exceeds 65504, the largest coefficient the float path's f16 "
+                             "hi/lo split can carry")
         return w
 
     def algorithmic_bytes(self):

@@ -195,6 +195,29 @@ int bf_pipeline_set_delays(bf_pipeline* p, const float* host_delay_vals) {
   return st;
 }
 
+int bf_check_gains(const float* host_gains, int M, int A, int flags) {
+  BF_REQUIRE(host_gains != nullptr && M > 0 && A > 0, "bf_check_gains: null pointer or bad shape M=%d A=%d", M, A);
+  double gmax = 0.0;
+  const size_t n = static_cast<size_t>(M) * A;
+  for (size_t i = 0; i < n; ++i) {
+    const double g = std::fabs(static_cast<double>(host_gains[i]));
+    BF_REQUIRE(std::isfinite(g), "bf_check_gains: weight %zu is not finite", i);
+    gmax = g > gmax ? g : gmax;
+  }
+  if ((flags & BF_FUSED_OUT_INT8) && !(flags & BF_FUSED_INT8_VIA_F32)) {
+    // the Q14 integer path: the weights must keep the high limb int8 and the int32 sums from wrapping
+    BF_REQUIRE(bf::q14_sum_bound_ok(A, flags & BF_FUSED_SIGNED, gmax),
+               "bf_check_gains: weight magnitude %g out of range for int8 beams with %d inputs", gmax, A);
+  } else {
+    // the float path: f16(w) of the coefficients' hi/lo split is infinite from 65520 on
+    BF_REQUIRE(gmax <= 65504.0,
+               "bf_check_gains: weight magnitude %g exceeds 65504, the largest coefficient the float path's f16 hi/lo "
+               "split can carry", gmax);
+  }
+  bf::clear_error();
+  return BF_OK;
+}
+
 int bf_pipeline_set_gains(bf_pipeline* p, const float* host_gains) {
   BF_REQUIRE(p != nullptr, "bf_pipeline_set_gains: null pipeline");
   BF_GUARD(p);
@@ -203,18 +226,7 @@ int bf_pipeline_set_gains(bf_pipeline* p, const float* host_gains) {
     bf::clear_error();
     return BF_OK;
   }
-  if ((p->flags & BF_FUSED_OUT_INT8) && !(p->flags & BF_FUSED_INT8_VIA_F32)) {
-    // the Q14 integer path: the weights must keep the high limb int8 and the int32 sums from wrapping
-    double gmax = 0.0;
-    const size_t n = static_cast<size_t>(p->M) * p->A;
-    for (size_t i = 0; i < n; ++i) {
-      const double g = std::fabs(static_cast<double>(host_gains[i]));
-      BF_REQUIRE(std::isfinite(g), "bf_pipeline_set_gains: weight %zu is not finite", i);
-      gmax = g > gmax ? g : gmax;
-    }
-    BF_REQUIRE(bf::q14_sum_bound_ok(p->A, p->flags & BF_FUSED_SIGNED, gmax),
-               "bf_pipeline_set_gains: weight magnitude %g out of range for int8 beams with %d inputs", gmax, p->A);
-  }
+  if (const int st = bf_check_gains(host_gains, p->M, p->A, p->flags); st != BF_OK) return st;
   const int st = upload(p, host_gains, p->h_gains, p->d_gains, p->gain_bytes, p->ev_gains, &p->n_gain_updates);
   if (st == BF_OK) p->gains_set = true;
   return st;

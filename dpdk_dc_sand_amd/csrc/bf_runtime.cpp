@@ -100,7 +100,8 @@ const char* bf_last_kernel(void) { return bf::g_last_kernel.c_str(); }
 int bf_abi_version(void) { return 302; }
 
 int bf_has_feature(const char* name) {
-  for (const char* f : {"incoherent_beam", "beam_detect", "voltage_stats", "last_kernel", "fused_plan", "correlate"})
+  for (const char* f : {"incoherent_beam", "beam_detect", "voltage_stats", "last_kernel", "fused_plan", "correlate",
+                        "check_gains"})
     if (name && std::strcmp(name, f) == 0) return 1;
   return 0;
 }

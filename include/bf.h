@@ -40,10 +40,10 @@ const char* bf_last_error(void);
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
  * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
- * bf_correlate and bf_correlate_algorithmic_bytes. */
+ * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan", "correlate"), 0 for any other name (and for NULL). */
+ * "fused_plan", "correlate", "check_gains"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -159,7 +159,16 @@ int bf_reorder(const uint8_t* in, uint8_t* out, int B, int A, int C, int T, void
  * Replaces MatrixMultiply._run -> ComplexMultKernel.complex_mult -> run_complex_mult
  * (beamformer/beamforming/matrix_multiply.py:155-163, complex_mult_kernel.py:11-100, 106-162):
  *   x : 8-bit (B, P, C, NB, 16, A, 2)   w : f32 (B, P, C, 2A, 2M)   y : f32 (B, P, C, NB, 16, 2M)
- *   y[..., col] = sum_k x[..., k] * w[k, col] with x[2a] = re, x[2a+1] = im. */
+ *   y[..., col] = sum_k x[..., k] * w[k, col] with x[2a] = re, x[2a+1] = im.
+ * Float coefficient domain and floor (this entry point's table, and the float beams of bf_beamform_fused* -- float
+ * output and BF_FUSED_INT8_VIA_F32 -- whose coefficients are g * (cos, sin)): every coefficient enters the MFMA as
+ * hi = f16(w), lo = f16(w - hi).  The domain is |w| <= 65504: from 65520 on f16(w) is infinite and the beams are inf or
+ * NaN (this call, which reads its table on the device, does not check; bf_check_gains and the Python wrapper do for
+ * weights).  The pair carries w with an error of at most 2^-22 |w| + 2^-25, the second term an absolute floor from
+ * f16's subnormal spacing: weights near 1 are f32-class (about 5e-9 of sum |x w| over 256 antennas), but weights far
+ * below 1 lose accuracy relative to their own size -- 1e-6 at 2^-8 (a table normalised by 1 / 256 antennas), 1.6e-5
+ * at 2^-12, 2e-4 at 2^-16, 4e-3 at 2^-20.  Normalise weights and tables to a maximum of about 1 and fold the common
+ * factor into out_scale or a later stage. */
 int bf_beamform(const uint8_t* x, const float* w, float* y, int B, int P, int C, int NB, int A, int M,
                 int sample_signed, void* stream);
 
@@ -207,11 +216,18 @@ int bf_beamform_fused(const uint8_t* raw, const float* delay_vals, int delay_cha
  * BF_FUSED_OUT_INT8 the Q14 integer path needs |g| <= 1.992 (the high limb stays int8) and
  * A*max|x|*(sqrt(2)*max|g|*2^14 + 1) < 2^31 (no int32 overflow; max|x| = 128 signed, 255 unsigned); the Python
  * wrapper, which owns the host copy of the weights, checks both.  Without gains the library checks the unit-gain
- * bound itself (A <= 363 unsigned, A <= 724 signed) and returns BF_ERR_ARG beyond it. */
+ * bound itself (A <= 363 unsigned, A <= 724 signed) and returns BF_ERR_ARG beyond it.  Float beams (float output and
+ * BF_FUSED_INT8_VIA_F32) need |g| <= 65504 and are f32-class only for weights of order 1: the float coefficient
+ * domain and floor at bf_beamform.  bf_check_gains checks a host copy of the table against whichever bound applies. */
 int bf_beamform_fused_weighted(const uint8_t* raw, const float* delay_vals, int delay_channels, const float* gains,
                                void* y, int B, int C, int T, int A, int M, int Ctot, int xeng_id,
                                double sample_period, double t0, double batch_dt, int flags, float out_scale,
                                void* stream);
+/* The weight bounds of bf_beamform_fused_weighted for the contract `flags` selects, checked on a HOST copy of the
+ * (M, A) table (pure host code, no device): every weight finite; the Q14 integer contract's two conditions above; for
+ * float beams max|g| <= 65504.  BF_ERR_ARG with the reason in bf_last_error otherwise.  bf_pipeline_set_gains applies
+ * it; a caller of the device-pointer entry points, which cannot read the table, calls it before uploading. */
+int bf_check_gains(const float* host_gains, int M, int A, int flags);
 
 /* bf_beamform_fused_weighted with a caller-owned device workspace (the fused call itself never allocates).  With at
  * least bf_fused_workspace_bytes(...) bytes, the int8 beams of many antennas x beams (config 4: the 32-beam integer
@@ -371,7 +387,9 @@ int bf_pipeline_create(bf_pipeline** out, int B, int C, int T, int A, int M, int
 int bf_pipeline_destroy(bf_pipeline* p);
 int bf_pipeline_frame_bytes(const bf_pipeline* p, size_t* in_bytes, size_t* out_bytes);
 int bf_pipeline_set_delays(bf_pipeline* p, const float* host_delay_vals);  /* host f32 (Cd, M, A, 4) */
-int bf_pipeline_set_gains(bf_pipeline* p, const float* host_gains);        /* host f32 (M, A); NULL = unit */
+/* host f32 (M, A); NULL = unit.  Refuses (BF_ERR_ARG) what bf_check_gains refuses for the pipeline's flags: for float
+ * pipelines max|g| > 65504 (the float coefficient domain and floor at bf_beamform). */
+int bf_pipeline_set_gains(bf_pipeline* p, const float* host_gains);
 int bf_pipeline_submit(bf_pipeline* p, const void* host_in, void* host_out, double t0, double batch_dt,
                        long long* ticket);
 int bf_pipeline_wait(bf_pipeline* p, long long ticket, int stage);         /* stage 0 input, 1 output */

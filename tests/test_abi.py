@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 
 from dpdk_dc_sand_amd import _lib
@@ -124,6 +125,44 @@ def test_kernel_path_and_contract_flags_are_validated():
     big = [fake, fake, 1, fake, 1, 4, 16, 364, 1, 1024, 0, 1e-9, 0.0, 0.0]
     with pytest.raises(_lib.BeamformerError, match="overflows"):
         _lib.call("bf_beamform_fused", *big, _lib.FUSED_OUT_INT8, 1.0, None)
+
+
+def test_gain_bounds_are_checked_on_the_host():
+    """bf_check_gains, the check bf_pipeline_set_gains applies to its host table: the Q14 contract's bounds for int8
+    beams, and for float beams (float output, BF_FUSED_INT8_VIA_F32) the f16 hi/lo split's domain |g| <= 65504."""
+    M, A = 2, 300
+
+    def check(g, flags):
+        g = np.ascontiguousarray(g, np.float32)
+        return _lib.call("bf_check_gains", g.ctypes.data, M, A, flags)
+
+    assert _lib.load().bf_has_feature(b"check_gains") == 1
+    q14, via_f32 = _lib.FUSED_OUT_INT8, _lib.FUSED_OUT_INT8 | _lib.FUSED_INT8_VIA_F32
+    check(np.ones((M, A)), q14)  # uint8: 300 * 255 * (sqrt2 * 2^14 * g + 1) < 2^31 holds at g = 1, fails at 1.5
+    for bad in (1.5, 2.5):
+        with pytest.raises(_lib.BeamformerError, match="out of range for int8 beams") as e:
+            check(np.full((M, A), bad), q14)
+        assert e.value.status == -1
+    top = np.ones((M, A), np.float32)
+    top[1, 7], top[0, 0] = 65504.0, -65504.0
+    for flags in (0, _lib.FUSED_SIGNED | _lib.FUSED_EXACT_COEFF, via_f32):
+        check(np.full((M, A), 2.5), flags)
+        check(top, flags)  # exactly the largest f16: accepted
+        for bad in (65520.0, -1e30, float(np.nextafter(np.float32(65504), np.float32(np.inf)))):
+            over = top.copy()
+            over[1, 299] = bad
+            with pytest.raises(_lib.BeamformerError, match="f16 hi/lo split") as e:
+                check(over, flags)
+            assert e.value.status == -1 and "65504" in e.value.message
+    for flags in (0, q14, via_f32):
+        nan = np.ones((M, A), np.float32)
+        nan[1, 7] = np.nan
+        with pytest.raises(_lib.BeamformerError, match="weight 307 is not finite"):
+            check(nan, flags)
+    with pytest.raises(_lib.BeamformerError, match="null pointer or bad shape"):
+        _lib.call("bf_check_gains", None, M, A, 0)
+    with pytest.raises(_lib.BeamformerError, match="null pointer or bad shape"):
+        _lib.call("bf_check_gains", top.ctypes.data, 0, A, 0)
 
 
 def test_template_int8_overflow_bound():

@@ -198,7 +198,13 @@ def test_stream_gain_bound_checked_by_the_library(context):
     f32 = StreamingBeamformerTemplate(context, 1, 2, 4, 16, A, M, delay_channels=1, out_int8=True, int8_contract="f32",
                                       depth=2)
     with f32.instantiate() as sb:
-        _lib.call("bf_pipeline_set_gains", sb._h, np.full((M, A), 2.5, np.float32).ctypes.data)
+        # the float contract's own bound: the f16 hi/lo split of the coefficients carries |g| <= 65504
+        # (the tables are named: the library reads them now, and a temporary's .ctypes.data would dangle)
+        fine, top, over = (np.full((M, A), g, np.float32) for g in (2.5, -65504.0, 65520.0))
+        _lib.call("bf_pipeline_set_gains", sb._h, fine.ctypes.data)
+        _lib.call("bf_pipeline_set_gains", sb._h, top.ctypes.data)
+        with pytest.raises(_lib.BeamformerError, match="f16 hi/lo split"):
+            _lib.call("bf_pipeline_set_gains", sb._h, over.ctypes.data)
 
 
 def test_stream_errors(context):

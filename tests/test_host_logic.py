@@ -125,6 +125,16 @@ def test_beam_weights_request_semantics():
     i8.set_beam_weights(0, 1.992, -1.992, 0, 0, 0)
     with pytest.raises(ValueError, match="out of range"):
         i8.set_beam_weights(0, 2.0, 0, 0, 0, 0)
+    # float beams (and int8_contract="f32"): the f16 hi/lo split of the coefficients carries |g| <= 65504 exactly;
+    # beyond it the beams would be inf or NaN, so the weights are refused
+    for kw in (dict(), dict(out_int8=True, int8_contract="f32")):
+        f = FusedBeamformerTemplate(None, 1, 4, 4, 16, 5, 3, beam_weights=True, **kw).instantiate(FakeQueue())
+        f.set_beam_weights(1, 65504.0, -65504.0, 2.0 ** -20, 0, 1)
+        np.testing.assert_array_equal(f.beam_weights()[1], np.float32([65504, -65504, 2.0 ** -20, 0, 1]))
+        for bad in (65536.0, -65520.0, float(np.nextafter(np.float32(65504), np.float32(np.inf)))):
+            with pytest.raises(ValueError, match="f16 hi/lo split"):
+                f.set_beam_weights(2, 1, 1, bad, 1, 1)
+        np.testing.assert_array_equal(f.beam_weights()[2], 1)  # a refused table is not kept
     with pytest.raises(ValueError, match="without beam_weights"):
         FusedBeamformerTemplate(None, 1, 4, 4, 16, 5, 3).instantiate(FakeQueue()).set_beam_weights(0, *[1] * 5)
 
