@@ -47,10 +47,12 @@ __device__ __forceinline__ double steering_rotation(float4 dv, double ch, const 
   return initial - centre;
 }
 
-// float64 sin and cos for |x| < ~1e5: Cody-Waite reduction by pi/2 (three-part constant, fma) and the fdlibm
-// minimax kernels on [-pi/4, pi/4].  Within 1 ulp of libm; the float32 roundings of cos and sin matched libm's
-// on all 7e7 probe arguments (tools/probes/sincos_check.c), at about a fifth of the generic sincos' cost (no
-// Payne-Hanek path, no double-double reduction).  Steering phases are |rot| < ~1e3.
+// float64 sin and cos: Cody-Waite reduction by pi/2 (three-part constant, fma) and the fdlibm minimax kernels on
+// [-pi/4, pi/4].  Within 1 ulp of libm; the float32 roundings of cos and sin matched libm's on all 7e7 probe
+// arguments, |x| < ~1e5 (tools/probes/sincos_check.c), at about a fifth of the generic sincos' cost (no Payne-Hanek
+// path, no double-double reduction).  The first reduction step is one fma and the three parts carry pi/2 to 1e-49,
+// so the reduced argument stays good to ~1e-16 far beyond the probed range: telescope-scale steering phases reach
+// |rot| ~ 2e5, day-old models 5e6 (bit for bit against libm in tests/test_gpu_phase_domain.py).
 __device__ __forceinline__ void sincos_pio2(double x, double* s, double* c) {
 #pragma clang fp contract(off)
   const double n = rint(x * 0.63661977236758138);  // 2 / pi

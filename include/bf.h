@@ -187,6 +187,23 @@ int bf_beamform(const uint8_t* x, const float* w, float* y, int B, int P, int C,
  *                           int32 sums, q = sat127(rne(f32(y) * out_scale * 2^-14)); integer MFMA, bit-exact;
  *   BF_FUSED_INT8_VIA_F32 : q = sat127(rne(y_f32 * out_scale)) of the float32 beams (the reference's float32
  *                           coefficient arithmetic, requantised in-kernel == bf_requant of the float output).
+ * The steering argument's domain.  With tau' = tau + tau_rate*dt_b and phi' = phi + phi_rate*dt_b (float64) the phase
+ * of channel ch is rot = phi' + tau' * (ch - Ctot/2) * K, K = -pi / (Ctot * sample_period); Ctot may be odd, and the
+ * call's channels may lie anywhere in the band, the centre channel (where the delay term vanishes) included.
+ *   int8 beams (Q14 contract): the bits are the contract's for every finite model.  A coefficient is evaluated by the
+ *     fast phasor while mag = |f32(tau')| * f32((ch + Ctot/2) * |K|) + |f32(phi')| < 2e5 -- at the top of the band that
+ *     is |tau'| < 4.2e4 samples less |phi'| / 4.7, at its bottom 1.3e5 samples, and |phi'| < 2e5 rad (a model 2.8 hours
+ *     old at a fringe rate of 20 rad/s) -- and otherwise, or where the fast value lies within 5e-10 of a rounding
+ *     decision, exactly (float64 in the reference's operation order): the same bits, slower (a wave runs as many exact
+ *     passes as its most-flagged lane needs).  An 8 km array at L-band (+-4.6e4 samples) keeps most of the band
+ *     on the fast phasor; beyond mag = 2e5 every coefficient is exact.
+ *   float beams, BF_FUSED_EXACT_COEFF: bit-exact to bf_coeff_gen / bf_coeff_gen_time at any finite argument.
+ *   float beams, fast phasor (default): rot is reduced to revolutions in float64 and rounded once to float32, so the
+ *     phasor's error is <= 2^-22 (argument rounding 2^-26 rev plus the hardware sin / cos) + 4 * 2^-53 * |rot|: flat
+ *     in |rot| up to about 1e8 rad (measured flat from |rot| < 1e2 to 5e6, tests/test_gpu_phase_domain.py), far beyond
+ *     any delay a telescope tracks.
+ *   A model with a NaN or an infinity in any field has no contract: no output is defined for it (the int8 path's
+ *     range check sends it to the exact path, which returns whatever float64 arithmetic gives).
  * Kernel-path and workgroup-order overrides (BF_FUSED_PATH_*, BF_FUSED_ORDER_*) exist for tests and measurement:
  * every path computes the same contract, a path that does not fit the shape falls through to one that does, and
  * 0 (automatic) picks the fastest path for the shape.  The library never reads the environment. */

@@ -21,7 +21,8 @@ and `verdict` demands all of
     5. KERNEL  the kernel that ran (bf_last_kernel) is the one the case claims to cover.
 
 The verdict is pure NumPy over host byte arrays (tests/test_guarded_host.py runs it over NumPy stand-ins for a kernel);
-`DeviceExecutor` is the thin upload / launch / download wrapper for the GPU cases.
+`DeviceExecutor` is the thin upload / launch / download wrapper for the GPU cases, and `fused_ws` the guarded
+bf_beamform_fused_ws call that tests/test_gpu_edges.py and tests/test_gpu_phase_domain.py share.
 
 Limits: the harness never hands a kernel a pointer or size its header forbids and never depends on a fault.  An overrun
 of up to G bytes on either side of a payload lands in memory the test owns and is reported; anything that strays
@@ -180,3 +181,28 @@ class DeviceExecutor:
         finally:
             for p in base.values():
                 lib.load().bf_free(ctypes.c_void_p(p))
+
+
+def fused_ws(ex, c, raw, d, gains, out_dtype, oracle, Ctot, xeng_id, Ts, t0, batch_dt):
+    """One guarded bf_beamform_fused_ws call of a case (the fields of fused_cases.Call: A M T B C flags expect scale
+    workspace, and dch gains for the planner) in the band (Ctot, xeng_id, Ts) at steering times t0 + b batch_dt:
+    guards, two fills, the expected kernel name, and the plan asked on the host == the kernel that ran.
+    oracle(y) raises AssertionError on wrong beams.  Returns the beams."""
+    import fused_cases as FC
+    lib = ex._lib
+    dch = d.shape[0]
+    bufs = [inp("raw", raw, 16), inp("dv", d, 16), out("y", (c.B, 2, c.C, c.T // 16, 16, 2 * c.M), out_dtype, 16)]
+    if gains is not None:
+        bufs.append(inp("gains", gains, 4))
+    ws_bytes = FC.workspace_bytes(c)
+    if c.workspace:
+        assert ws_bytes > 0, "the case expects a shape that uses the workspace"
+        bufs.append(out("ws", (ws_bytes,), np.uint8, 16))
+
+    def launch(p):
+        lib.call("bf_beamform_fused_ws", p["raw"], p["dv"], dch, p.get("gains"), p["y"], c.B, c.C, c.T, c.A, c.M, Ctot,
+                 xeng_id, Ts, t0, batch_dt, c.flags, c.scale, p.get("ws"), ws_bytes, ex.queue.handle)
+
+    y = run_case(ex, bufs, launch, lambda outs: oracle(outs["y"]), c.expect)["y"]
+    assert FC.planned_name(c) == lib.load().bf_last_kernel().decode()  # the plan, asked on the host, is what ran
+    return y

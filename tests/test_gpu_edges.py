@@ -16,7 +16,6 @@ import numpy as np
 import pytest
 
 import edge_cases as EC
-import fused_cases as FC
 import guarded as gd
 import oracle as O
 from dpdk_dc_sand_amd import _lib
@@ -32,23 +31,7 @@ def ex(context, command_queue):
 
 def fused_ws(ex, c, raw, d, gains, out_dtype, oracle):
     """One guarded bf_beamform_fused_ws call of a case (fused_cases.Call or edge_cases.Case); returns the beams."""
-    dch = d.shape[0]
-    bufs = [gd.inp("raw", raw, 16), gd.inp("dv", d, 16),
-            gd.out("y", (c.B, 2, c.C, c.T // 16, 16, 2 * c.M), out_dtype, 16)]
-    if gains is not None:
-        bufs.append(gd.inp("gains", gains, 4))
-    ws_bytes = FC.workspace_bytes(c)
-    if c.workspace:
-        assert ws_bytes > 0, "the case expects a shape that uses the workspace"
-        bufs.append(gd.out("ws", (ws_bytes,), np.uint8, 16))
-
-    def launch(p):
-        _lib.call("bf_beamform_fused_ws", p["raw"], p["dv"], dch, p.get("gains"), p["y"], c.B, c.C, c.T, c.A, c.M, CTOT,
-                  XENG, TS, T0, BDT, c.flags, c.scale, p.get("ws"), ws_bytes, ex.queue.handle)
-
-    y = gd.run_case(ex, bufs, launch, lambda outs: oracle(outs["y"]), c.expect)["y"]
-    assert FC.planned_name(c) == _lib.load().bf_last_kernel().decode()  # the plan, asked on the host, is what ran
-    return y
+    return gd.fused_ws(ex, c, raw, d, gains, out_dtype, oracle, CTOT, XENG, TS, T0, BDT)
 
 
 # ---- integer beams ------------------------------------------------------------------------------------------------
