@@ -96,6 +96,9 @@ PROTOTYPES = {
     "bf_vstats_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_correlate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "bf_correlate_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_beam_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                c_void_p]),
+    "bf_beam_streams_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -124,6 +127,8 @@ VSTATS_SIGNED = 1
 VSTATS_POWER, VSTATS_SK, VSTATS_FLAGS = 1, 2, 4
 # bf_correlate flags
 CORR_SIGNED, CORR_ACCUMULATE = 1, 2
+# bf_beam_streams flags (BSTREAM_LIST: a beam list is given; the byte count's only way to know)
+BSTREAM_IN_INT8, BSTREAM_REQUANT, BSTREAM_LIST = 1, 2, 4
 
 
 class BeamformerError(RuntimeError):

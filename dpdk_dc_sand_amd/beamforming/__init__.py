@@ -15,10 +15,13 @@ BeamDetectorTemplate / BeamDetector (Stokes I or IQUV power of the beams, integr
 FusedBeamformer.outData), beamforming.vstats -> VoltageStatsTemplate / VoltageStats (per-antenna power, spectral
 kurtosis and RFI flags of the same raw voltages; antenna_mask_from_flags turns the flags into an antenna mask),
 beamforming.correlate -> CorrelatorTemplate / Correlator (integer visibilities of every antenna pair of the same raw
-voltages; n_baselines, baseline_index and visibility_matrix read the triangular output).
+voltages; n_baselines, baseline_index and visibility_matrix read the triangular output), beamforming.beam_streams ->
+BeamStreamsTemplate / BeamStreams (the beams of FusedBeamformer.outData as per-beam voltage streams (B, K, C, T, 2, 2),
+any subset; the int8 streams bind to VoltageStats, Correlator and IncoherentBeam as K antennas).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
+from .beam_streams import BeamStreams, BeamStreamsTemplate  # noqa: F401
 from .beamform_op_sequence import OpSequence, OpSequenceTemplate  # noqa: F401
 from .coeff_generator import CoeffGenerator, CoeffGeneratorTemplate  # noqa: F401
 from .complex_mult_kernel import ComplexMultKernel  # noqa: F401

@@ -40,10 +40,11 @@ const char* bf_last_error(void);
  * the 3.2 library it loaded has them: "incoherent_beam" = bf_incoherent_beam and bf_incoherent_algorithmic_bytes,
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
  * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
- * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains. */
+ * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains, "beam_streams" = bf_beam_streams and
+ * bf_beam_streams_algorithmic_bytes. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan", "correlate", "check_gains"), 0 for any other name (and for NULL). */
+ * "fused_plan", "correlate", "check_gains", "beam_streams"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -69,6 +70,7 @@ const char* bf_last_kernel(void);
  *   bf_beam_detect                    beams 16, out 4
  *   bf_voltage_stats                  raw 16, out_power 4, out_sk 4, out_flags 1 (none)
  *   bf_correlate                      raw 16, out 4
+ *   bf_beam_streams                   beams 16, beam_index 4 (or NULL), out 16
  *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -388,6 +390,39 @@ double bf_vstats_algorithmic_bytes(int B, int C, int T, int A, int tint, int out
 int bf_correlate(const uint8_t* raw, int32_t* out, int B, int C, int T, int A, int tint, int bint, int flags,
                  void* stream);
 double bf_correlate_algorithmic_bytes(int B, int C, int T, int A, int tint, int bint, int flags);
+
+/* Beam streams (no reference counterpart: the reference has a PreBeamformReorder and nothing after the contraction):
+ * the beams as per-beam voltage streams, any subset, each with the shape and sample order of one antenna of the voltage
+ * cube -- what one subscriber, recorder or multicast group of a beam consumes, and what bf_voltage_stats, bf_correlate
+ * and bf_incoherent_beam (int8, their signed flags) read directly with A = K:
+ *   beams      : (B, 2, C, T/16, 16, 2M), f32, or int8 with BF_BSTREAM_IN_INT8 (the fused operator's output; column
+ *                2m = re, 2m+1 = im)
+ *   beam_index : int32 (K,) on the device, or NULL = the identity (then K must equal M)
+ *   out        : (B, K, C, T, 2, 2), last axes (pol, (re, im)); the dtype of `beams`, or int8 with BF_BSTREAM_REQUANT
+ *                (f32 beams only)
+ *   m = beam_index[k]  (k, when NULL)
+ *   out[b][k][c][t][p][z] = beams[b][p][c][t/16][t%16][2m + z]     if 0 <= m < M
+ *                         = 0 (all bits zero)                      otherwise
+ *   with BF_BSTREAM_REQUANT: out = clamp(rne(f32(beam value) * scale), -127, 127), bf_requant's formula (NaN -> -127).
+ * A copy moves bits and nothing else: a NaN payload, -0.0 and -128 arrive unchanged.  The list may repeat beams, be in
+ * any order and be longer than M; an index outside [0, M) is defined (the entry point cannot see a device list): its
+ * stream is zero and nothing outside `beams` is read.  Every output element is written once by one thread (no atomics:
+ * `out` need not be zeroed), the input is never written, two launches give identical bytes.  B, C, T, M, K >= 1;
+ * T % 16 == 0, T <= 2^20; M <= 4096, K <= 4096; scale finite and > 0 with BF_BSTREAM_REQUANT (ignored without); beams
+ * and out 16-byte, beam_index 4-byte aligned.  Refused with BF_ERR_ARG before any launch: unknown flag bits,
+ * BF_BSTREAM_REQUANT with BF_BSTREAM_IN_INT8, beam_index NULL with K != M (or with BF_BSTREAM_LIST), misalignment, a
+ * grid above 2^31 - 1 workgroups.
+ * bf_beam_streams_algorithmic_bytes: es_in * B*2*C*T*2M input bytes -- the whole cube once for any list: the cost of a
+ * dense read, a sparse list could read less -- plus es_out * B*K*C*T*4 output bytes, plus 4K list bytes with
+ * BF_BSTREAM_LIST (this function sees no pointer: the bit says that a list is given; without it K must equal M);
+ * es = 1 for int8, 4 for f32.  0 for any shape or flags bf_beam_streams refuses. */
+#define BF_BSTREAM_IN_INT8 1  /* beams are int8 (the fused operator's BF_FUSED_OUT_INT8 output), else f32 */
+#define BF_BSTREAM_REQUANT 2  /* f32 beams, int8 streams */
+#define BF_BSTREAM_LIST 4     /* a beam list is given: optional for bf_beam_streams (beam_index says it), the byte
+                                 count's only way to know */
+int bf_beam_streams(const void* beams, const int32_t* beam_index, void* out, int B, int C, int T, int M, int K,
+                    int flags, float scale, void* stream);
+double bf_beam_streams_algorithmic_bytes(int B, int C, int T, int M, int K, int flags);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

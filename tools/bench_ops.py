@@ -12,7 +12,10 @@ and 16, all three outputs and the power alone, each line with the stream ceiling
 beam on the same cube at the same integration, all in one process.  `--correlate` runs the correlator alone, at cfg3
 (integration T over all 8 batches) and cfg4 (integration T), each line with the stream ceiling for its own bytes and the
 useful int8 operation rate (NBL * 4 * 8 operations per channel-sample), then the incoherent beam on the same cube in
-the same process; its lines also go to `--out` (profiles/correlate_ops.jsonl).
+the same process; its lines also go to `--out` (profiles/correlate_ops.jsonl).  `--beam-streams` runs the beam streams
+alone, at cfg2, cfg3 and cfg4: int8, f32 and f32 requantised beams of the configuration's shape, every beam and one beam
+of M, medians of `--reps` launches, each line with the stream ceiling for its own bytes and bf_reorder on a voltage cube
+of the same byte count, in the same process; its lines also go to `--out` (profiles/beam_streams_ops.jsonl).
 """
 import argparse
 import ctypes
@@ -27,7 +30,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import _lib, accel  # noqa: E402
-from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, CoeffGeneratorTemplate,  # noqa: E402
+from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, BeamStreamsTemplate, CoeffGeneratorTemplate,  # noqa: E402
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
                                           PreBeamformReorderTemplate, VoltageStatsTemplate, CorrelatorTemplate)
 
@@ -270,6 +273,69 @@ def run_correlate(ctx, q, name, c, reps, rng, bint):
     measure(f"incoherent_tint{T}", IncoherentBeamTemplate(ctx, B, C, T, A, integration=T), "outData")
 
 
+def median_time(queue, fn, reps, settle_s=0.2):
+    """Per-launch HIP-event times of `reps` launches after the clock settle: (median, min, max) seconds."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < settle_s:
+        for _ in range(4):
+            fn()
+        queue.finish()
+    events = [(accel.Event(), accel.Event()) for _ in range(reps)]
+    for e0, e1 in events:
+        e0.record(queue)
+        fn()
+        e1.record(queue)
+    queue.finish()
+    times = sorted(e1.time_since(e0) for e0, e1 in events)
+    return float(np.median(times)), times[0], times[-1]
+
+
+def run_beam_streams(ctx, q, name, c, reps):
+    """The beam streams over beams of the configuration's shape (device-made random bytes): int8, f32 and f32
+    requantised, every beam (no list) and one beam of M (a list of one), medians of `reps` launches.  Each line carries
+    the stream ceiling for its own read and write bytes, and the drop-in bf_reorder on a voltage cube of the same byte
+    count as the beams (A = M for int8 beams, 4 M for f32: the project's other transpose, moving the same bytes as
+    the every-beam copy), all in one process."""
+    M, C, T, B = c["M"], c["C"], c["T"], c["B"]
+    shape = (B, 2, C, T // 16, 16, 2 * M)
+    for form, in_int8, requant in (("i8", True, False), ("f32", False, False), ("f32q", False, True)):
+        beams = accel.DeviceArray(ctx, shape, np.int8 if in_int8 else np.float32)
+        _lib.call("bf_fill_random", beams.ptr, beams.nbytes, 7, q.handle)
+        reorder = None
+        if not requant:  # bf_reorder on (B, A, C, T, 2, 2) of beams.nbytes, into a cube of the same size
+            A = M if in_int8 else 4 * M
+            assert B * A * C * T * 4 == beams.nbytes
+            dst = accel.DeviceArray(ctx, (beams.nbytes,), np.uint8)
+
+            def fn():
+                _lib.call("bf_reorder", beams.ptr, dst.ptr, B, A, C, T, q.handle)
+            reorder = median_time(q, fn, reps) + (A, _lib.load().bf_last_kernel().decode())
+            del dst
+        for label, index in (("all", None), ("one", [M // 2])):
+            tmpl = BeamStreamsTemplate(ctx, B, C, T, M, in_int8=in_int8, requantise=requant, scale=1 / 64, beams=index)
+            op = tmpl.instantiate(q)
+            op.bind(inBeams=beams)
+            op.ensure_all_bound()
+            t, t_min, t_max = median_time(q, op, reps)
+            kernel = _lib.load().bf_last_kernel().decode()
+            read_bytes = beams.nbytes + (4 * len(index) if index else 0)
+            write_bytes = op.buffer("outStreams").nbytes
+            assert tmpl.algorithmic_bytes() == read_bytes + write_bytes
+            del op
+            ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+            extra = {}
+            if reorder is not None and index is None:
+                extra = dict(reorder_us=round(reorder[0] * 1e6, 2), reorder_min_us=round(reorder[1] * 1e6, 2),
+                             reorder_max_us=round(reorder[2] * 1e6, 2), reorder_ants=reorder[3],
+                             reorder_kernel=reorder[4], time_over_reorder=round(t / reorder[0], 4))
+            emit(name, f"beam_streams_{form}_{label}", t, tmpl.algorithmic_bytes(), form=form, beams=label,
+                 n_streams=tmpl.n_streams, reps=reps, min_us=round(t_min * 1e6, 2), max_us=round(t_max * 1e6, 2),
+                 read_bytes=read_bytes, write_bytes=write_bytes, kernel=kernel, ceiling_us=round(ct * 1e6, 2),
+                 ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+                 ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4), **extra)
+        del beams
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -281,18 +347,23 @@ def main():
                    "incoherent beam on the same cube")
     p.add_argument("--correlate", action="store_true", help="only the correlator, its stream ceiling and the "
                    "incoherent beam on the same cube")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "correlate_ops.jsonl"),
-                   help="--correlate: the file that receives the lines as well")
+    p.add_argument("--beam-streams", action="store_true", help="only the beam streams, their stream ceiling and "
+                   "bf_reorder on a cube of the same byte count")
+    p.add_argument("--out", default=None, help="--correlate, --beam-streams: the file that receives the lines as well "
+                   "(profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl)")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
-    if args.correlate:
+    if args.correlate or args.beam_streams:
         global EMIT_FILE
-        EMIT_FILE = open(args.out, "w")
+        default = "correlate_ops.jsonl" if args.correlate else "beam_streams_ops.jsonl"
+        EMIT_FILE = open(args.out or os.path.join(ROOT, "profiles", default), "w")
     for name in args.only.split(","):
-        if args.incoherent or args.detect or args.vstats or args.correlate:
+        if args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams:
+            if name in INCOHERENT_CONFIGS and args.beam_streams:
+                run_beam_streams(ctx, q, name, CONFIGS[name], args.reps)
             if name in CORRELATE_CONFIGS and args.correlate:
                 run_correlate(ctx, q, name, CONFIGS[name], args.reps, rng, **CORRELATE_CONFIGS[name])
             if name in VSTATS_CONFIGS and args.vstats:
