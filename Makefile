@@ -8,12 +8,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 SRCS     := $(CSRC)/bf_runtime.cpp $(CSRC)/bf_coeff.hip $(CSRC)/bf_reorder.hip $(CSRC)/bf_beamform.hip \
             $(CSRC)/bf_fused.hip $(CSRC)/bf_wide.hip $(CSRC)/bf_wide_i8.hip $(CSRC)/bf_q14table.hip $(CSRC)/bf_requant.hip \
             $(CSRC)/bf_study.hip $(CSRC)/bf_incoherent.hip $(CSRC)/bf_detect.hip $(CSRC)/bf_vstats.hip \
-            $(CSRC)/bf_correlate.hip $(CSRC)/bf_beam_streams.hip \
+            $(CSRC)/bf_correlate.hip $(CSRC)/bf_beam_streams.hip $(CSRC)/bf_dedisperse.hip \
             $(CSRC)/bf_pipeline.cpp $(CSRC)/bf_comm.cpp $(CSRC)/bf_fused_plan.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.hpp) include/bf.h
 
-.PHONY: all clean cabi stream
+.PHONY: all clean cabi stream dedisperse-naive
 all: $(LIB) cabi
 
 # bench.py's stream ceiling (the box's best plain stream over a kernel's byte mix): a small measurement library of its
@@ -21,6 +21,14 @@ all: $(LIB) cabi
 STREAM_LIB := build/libbf_stream.so
 stream: $(STREAM_LIB)
 $(STREAM_LIB): tools/stream_ceiling.hip tools/stream_kernels.hpp
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+
+# tools/bench_ops.py --dedisperse: the one-thread-per-output dedispersion the tiled kernel is measured against; a
+# measurement library of its own, never linked into the product.
+NAIVE_LIB := build/libbf_dedisperse_naive.so
+dedisperse-naive: $(NAIVE_LIB)
+$(NAIVE_LIB): tools/dedisperse_naive.hip
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 

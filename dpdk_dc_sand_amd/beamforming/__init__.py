@@ -17,7 +17,9 @@ kurtosis and RFI flags of the same raw voltages; antenna_mask_from_flags turns t
 beamforming.correlate -> CorrelatorTemplate / Correlator (integer visibilities of every antenna pair of the same raw
 voltages; n_baselines, baseline_index and visibility_matrix read the triangular output), beamforming.beam_streams ->
 BeamStreamsTemplate / BeamStreams (the beams of FusedBeamformer.outData as per-beam voltage streams (B, K, C, T, 2, 2),
-any subset; the int8 streams bind to VoltageStats, Correlator and IncoherentBeam as K antennas).
+any subset; the int8 streams bind to VoltageStats, Correlator and IncoherentBeam as K antennas),
+beamforming.dedisperse -> DedisperserTemplate / Dedisperser (DM-trial time series (M, D, N) of one Stokes plane of
+BeamDetector.outData over a device ring of the recent past; dispersion_lags makes the lag table).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
@@ -27,6 +29,7 @@ from .coeff_generator import CoeffGenerator, CoeffGeneratorTemplate  # noqa: F40
 from .complex_mult_kernel import ComplexMultKernel  # noqa: F401
 from .correlate import (Correlator, CorrelatorTemplate, baseline_index, n_baselines,  # noqa: F401
                         visibility_matrix)
+from .dedisperse import Dedisperser, DedisperserTemplate, dispersion_lags  # noqa: F401
 from .detect import BeamDetector, BeamDetectorTemplate  # noqa: F401
 from .fused import FusedBeamformer, FusedBeamformerTemplate  # noqa: F401
 from .incoherent import IncoherentBeam, IncoherentBeamTemplate  # noqa: F401

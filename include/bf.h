@@ -41,10 +41,10 @@ const char* bf_last_error(void);
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
  * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
  * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains, "beam_streams" = bf_beam_streams and
- * bf_beam_streams_algorithmic_bytes. */
+ * bf_beam_streams_algorithmic_bytes, "dedisperse" = bf_dedisperse and bf_dedisperse_algorithmic_bytes. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan", "correlate", "check_gains", "beam_streams"), 0 for any other name (and for NULL). */
+ * "fused_plan", "correlate", "check_gains", "beam_streams", "dedisperse"), 0 for any other name (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -71,6 +71,7 @@ const char* bf_last_kernel(void);
  *   bf_voltage_stats                  raw 16, out_power 4, out_sk 4, out_flags 1 (none)
  *   bf_correlate                      raw 16, out 4
  *   bf_beam_streams                   beams 16, beam_index 4 (or NULL), out 16
+ *   bf_dedisperse                     power 16, ring 16, lags 4, out 16
  *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -423,6 +424,37 @@ double bf_correlate_algorithmic_bytes(int B, int C, int T, int A, int tint, int 
 int bf_beam_streams(const void* beams, const int32_t* beam_index, void* out, int B, int C, int T, int M, int K,
                     int flags, float scale, void* stream);
 double bf_beam_streams_algorithmic_bytes(int B, int C, int T, int M, int K, int flags);
+
+/* Dedisperser (no reference counterpart): incoherent dedispersion of one Stokes plane of bf_beam_detect's output into
+ * one time series per beam and trial dispersion measure, over a caller-owned ring of the recent past:
+ *   power : f32 (B, S, K, J, M), exactly bf_beam_detect's out (K = C/fint, J = T/tint); only plane `plane` is read.  The
+ *           batches follow one another in time (as in bf_beamform_fused), so the call brings N = B*J new samples per
+ *           channel and beam, time index n = b*J + j
+ *   ring  : f32 (K, R, M), one slot per sample, beam fastest (the detector's own order); R a multiple of N; `head`, a
+ *           multiple of N in [0, R), is the slot of this call's first sample.  The caller zeroes the ring before the
+ *           first call and advances head' = (head + N) % R; the library keeps no state
+ *   lags  : int32 (D, K) on the device, lags[d][k] = how many samples back channel k is read for trial d.  Legal values
+ *           are 0 .. R - N; the entry point cannot see a device table, so the kernel clamps any other value into that
+ *           range and never reads outside the ring.  Any table in range is legal (monotone or not)
+ *   out   : f32 (M, D, N): one contiguous time series per beam and trial
+ * In stream order:
+ *   1. ring[k][(head + n) % R][m] = power[b][plane][k][j][m]              (bits copied; nothing else in ring changes)
+ *   2. acc[m][d][n] = sum over k = 0 .. K-1 of ring[k][(head + n - lags[d][k]) mod R][m]  (float64 sum of the f32 values)
+ *      out[m][d][n] = float32(acc * float64(scale))                       (one multiply, one round-to-nearest-even)
+ * The order of the float64 additions is the kernel's own and fixed: two launches give identical
+ * bytes; no atomics, `out` need not be zeroed, every element of `out` is written once by one thread; `power` and `lags`
+ * are never written.  If the ring holds integer-valued f32 below 2^24 (a detector fed int8 beams at scale 1 with
+ * tint * fint < 256), acc is exact in any order and out is bit-exact; for general f32 the result is within
+ * K * 2^-53 * sum|x| of the exact sum before the scaling and the float32 rounding.
+ * B, S, K, J, M, D >= 1; 0 <= plane < S; M <= 4096, D <= 4096; R >= N and R % N == 0; 0 <= head < R and head % N == 0;
+ * scale finite and > 0; power, ring and out 16-byte, lags 4-byte aligned; all element offsets are 64-bit (a ring of
+ * several GiB is normal).  Every refusal is BF_ERR_ARG before any launch.
+ * bf_dedisperse_algorithmic_bytes: span_sum = sum over k of (max over d of lags[d][k] - min over d of lags[d][k]), from
+ * the caller's host copy of the table; 4 * (2*K*N*M [the block read and appended] + (K*N + span_sum)*M [every ring
+ * sample some trial needs, once] + D*N*M [the output]); 0 for any shape bf_dedisperse refuses and for span_sum < 0. */
+int bf_dedisperse(const float* power, float* ring, const int32_t* lags, float* out, int B, int S, int plane, int K,
+                  int J, int M, int D, int R, int head, float scale, void* stream);
+double bf_dedisperse_algorithmic_bytes(int B, int K, int J, int M, int D, long long span_sum);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

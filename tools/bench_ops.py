@@ -16,6 +16,12 @@ the same process; its lines also go to `--out` (profiles/correlate_ops.jsonl).  
 alone, at cfg2, cfg3 and cfg4: int8, f32 and f32 requantised beams of the configuration's shape, every beam and one beam
 of M, medians of `--reps` launches, each line with the stream ceiling for its own bytes and bf_reorder on a voltage cube
 of the same byte count, in the same process; its lines also go to `--out` (profiles/beam_streams_ops.jsonl).
+`--dedisperse` runs the dedisperser alone, at cfg3 and cfg4: the detector-shaped power of the configuration at
+(tint, fint) = (16, 1), dispersion_lags over 856-1712 MHz at the 76.6 us sample time, 64 and 256 trials 1 pc cm^-3
+apart, medians of `--reps` launches; each line with the K*D*N*M additions per second, the stream ceiling for its own
+bytes, the telescope time one call covers (B*T / 208984 s) and the naive one-thread-per-output kernel
+(build/libbf_dedisperse_naive.so, `make dedisperse-naive`; step 2 only, no append) on the same ring in the same process;
+its lines also go to `--out` (profiles/dedisperse_ops.jsonl).
 """
 import argparse
 import ctypes
@@ -31,6 +37,7 @@ import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import _lib, accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, BeamStreamsTemplate, CoeffGeneratorTemplate,  # noqa: E402
+                                          DedisperserTemplate, dispersion_lags,
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
                                           PreBeamformReorderTemplate, VoltageStatsTemplate, CorrelatorTemplate)
 
@@ -336,6 +343,69 @@ def run_beam_streams(ctx, q, name, c, reps):
         del beams
 
 
+DEDISPERSE_CONFIGS = ("cfg3", "cfg4")
+SAMPLE_RATE = 208984.0  # channel samples per second: one call covers B * T / SAMPLE_RATE seconds
+
+
+def run_dedisperse(ctx, q, name, c, reps):
+    """The dedisperser over detector-shaped power of the configuration ((tint, fint) = (16, 1): K = C, J = T / 16), 64
+    and 256 trials 1 pc cm^-3 apart over 856-1712 MHz at 76.6 us samples, constant power and ring (0.747, the byte 0x3f
+    repeated).  Medians of `reps` launches; head advances from launch to launch as in use.  Each line carries the
+    additions per second, the stream ceiling for the algorithmic bytes, the telescope time of one call and the naive
+    kernel (step 2 only) on the same ring and lag table."""
+    M, C, T, B = c["M"], c["C"], c["T"], c["B"]
+    K, J = C, T // 16
+    N = B * J
+    path = os.path.join(ROOT, "build", "libbf_dedisperse_naive.so")
+    if not os.path.exists(path):
+        raise OSError(f"{path} not found: build it with `make dedisperse-naive`")
+    naive = ctypes.CDLL(path)
+    V, I = ctypes.c_void_p, ctypes.c_int
+    naive.bf_dedisperse_naive.restype = I
+    naive.bf_dedisperse_naive.argtypes = [V, V, V, I, I, I, I, I, I, ctypes.c_float, V]
+    freqs = 856e6 + 856e6 * np.arange(K) / K
+    power = accel.DeviceArray(ctx, (B, 1, K, J, M), np.float32)
+    _lib.call("bf_memset", power.ptr, 0x3f, power.nbytes, q.handle)
+    for D in (64, 256):
+        lags, latency = dispersion_lags(np.arange(D, dtype=np.float64), freqs, 76.6e-6)
+        tmpl = DedisperserTemplate(ctx, B, K, J, M, lags)
+        op = tmpl.instantiate(q)
+        op.bind(inPower=power)
+        op.ensure_all_bound()
+        op()  # allocates the ring and uploads the table
+        _lib.call("bf_memset", op.ring.ptr, 0x3f, op.ring.nbytes, q.handle)
+        t, t_min, t_max = median_time(q, op, reps)
+        kernel = _lib.load().bf_last_kernel().decode()
+        out = op.buffer("outData")
+
+        def fn():
+            st = naive.bf_dedisperse_naive(op.ring.ptr, op._lags.ptr, out.ptr, K, M, D, N, tmpl.ring_length, op.head,
+                                           1.0, q.handle)
+            if st != 0:
+                raise RuntimeError(f"bf_dedisperse_naive failed: hipError_t {st}")
+        tn, tn_min, tn_max = median_time(q, fn, reps)
+        alg = tmpl.algorithmic_bytes()
+        read_bytes = 4 * (K * N * M + (K * N + tmpl.span_sum) * M)
+        write_bytes = 4 * (K * N * M + D * N * M)
+        assert alg == read_bytes + write_bytes
+        ring_bytes = op.ring.nbytes
+        del op
+        ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+        adds = K * D * N * M
+        telescope = B * T / SAMPLE_RATE
+        emit(name, f"dedisperse_D{D}", t, alg, n_trials=D, n_channels=K, n_samples=N, n_beams=M, latency=latency,
+             ring_length=tmpl.ring_length, ring_bytes=ring_bytes, span_sum=tmpl.span_sum, reps=reps,
+             min_us=round(t_min * 1e6, 2), max_us=round(t_max * 1e6, 2), kernel=kernel, adds=adds,
+             Gadds_per_s=round(adds / t / 1e9, 1), read_bytes=read_bytes, write_bytes=write_bytes,
+             ceiling_us=round(ct * 1e6, 2), ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+             ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4),
+             telescope_us=round(telescope * 1e6, 1), times_real_time=round(telescope / t, 1),
+             naive_us=round(tn * 1e6, 2), naive_min_us=round(tn_min * 1e6, 2), naive_max_us=round(tn_max * 1e6, 2),
+             naive_Gadds_per_s=round(adds / tn / 1e9, 1), naive_includes_append=False,
+             naive_times_real_time=round(telescope / tn, 1), naive_over_tiled=round(tn / t, 3))
+    del power
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -349,19 +419,25 @@ def main():
                    "incoherent beam on the same cube")
     p.add_argument("--beam-streams", action="store_true", help="only the beam streams, their stream ceiling and "
                    "bf_reorder on a cube of the same byte count")
-    p.add_argument("--out", default=None, help="--correlate, --beam-streams: the file that receives the lines as well "
-                   "(profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl)")
+    p.add_argument("--dedisperse", action="store_true", help="only the dedisperser, its stream ceiling and the naive "
+                   "kernel on the same ring")
+    p.add_argument("--out", default=None, help="--correlate, --beam-streams, --dedisperse: the file that receives the "
+                   "lines as well (profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl, "
+                   "profiles/dedisperse_ops.jsonl)")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
-    if args.correlate or args.beam_streams:
+    if args.correlate or args.beam_streams or args.dedisperse:
         global EMIT_FILE
-        default = "correlate_ops.jsonl" if args.correlate else "beam_streams_ops.jsonl"
+        default = ("correlate_ops.jsonl" if args.correlate else
+                   "beam_streams_ops.jsonl" if args.beam_streams else "dedisperse_ops.jsonl")
         EMIT_FILE = open(args.out or os.path.join(ROOT, "profiles", default), "w")
     for name in args.only.split(","):
-        if args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams:
+        if args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams or args.dedisperse:
+            if name in DEDISPERSE_CONFIGS and args.dedisperse:
+                run_dedisperse(ctx, q, name, CONFIGS[name], args.reps)
             if name in INCOHERENT_CONFIGS and args.beam_streams:
                 run_beam_streams(ctx, q, name, CONFIGS[name], args.reps)
             if name in CORRELATE_CONFIGS and args.correlate:
