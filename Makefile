@@ -8,7 +8,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 SRCS     := $(CSRC)/bf_runtime.cpp $(CSRC)/bf_coeff.hip $(CSRC)/bf_reorder.hip $(CSRC)/bf_beamform.hip \
             $(CSRC)/bf_fused.hip $(CSRC)/bf_wide.hip $(CSRC)/bf_wide_i8.hip $(CSRC)/bf_q14table.hip $(CSRC)/bf_requant.hip \
             $(CSRC)/bf_study.hip $(CSRC)/bf_incoherent.hip $(CSRC)/bf_detect.hip $(CSRC)/bf_vstats.hip \
-            $(CSRC)/bf_correlate.hip $(CSRC)/bf_beam_streams.hip $(CSRC)/bf_dedisperse.hip \
+            $(CSRC)/bf_correlate.hip $(CSRC)/bf_beam_streams.hip $(CSRC)/bf_dedisperse.hip $(CSRC)/bf_pulse_search.hip \
             $(CSRC)/bf_pipeline.cpp $(CSRC)/bf_comm.cpp $(CSRC)/bf_fused_plan.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.hpp) include/bf.h

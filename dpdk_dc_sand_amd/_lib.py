@@ -102,6 +102,9 @@ PROTOTYPES = {
     "bf_dedisperse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_float, c_void_p]),
     "bf_dedisperse_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_longlong]),
+    "bf_pulse_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "bf_pulse_search_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),
@@ -132,6 +135,8 @@ VSTATS_POWER, VSTATS_SK, VSTATS_FLAGS = 1, 2, 4
 CORR_SIGNED, CORR_ACCUMULATE = 1, 2
 # bf_beam_streams flags (BSTREAM_LIST: a beam list is given; the byte count's only way to know)
 BSTREAM_IN_INT8, BSTREAM_REQUANT, BSTREAM_LIST = 1, 2, 4
+# bf_pulse_search flags
+PSEARCH_SERIES = 1
 
 
 class BeamformerError(RuntimeError):

@@ -19,7 +19,9 @@ voltages; n_baselines, baseline_index and visibility_matrix read the triangular 
 BeamStreamsTemplate / BeamStreams (the beams of FusedBeamformer.outData as per-beam voltage streams (B, K, C, T, 2, 2),
 any subset; the int8 streams bind to VoltageStats, Correlator and IncoherentBeam as K antennas),
 beamforming.dedisperse -> DedisperserTemplate / Dedisperser (DM-trial time series (M, D, N) of one Stokes plane of
-BeamDetector.outData over a device ring of the recent past; dispersion_lags makes the lag table).
+BeamDetector.outData over a device ring of the recent past; dispersion_lags makes the lag table),
+beamforming.pulse_search -> PulseSearchTemplate / PulseSearch (boxcar S/N of Dedisperser.outData against a running
+baseline: one peak record per (beam, trial) and one best record per beam; candidates decodes the read-back peaks).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
@@ -34,6 +36,7 @@ from .detect import BeamDetector, BeamDetectorTemplate  # noqa: F401
 from .fused import FusedBeamformer, FusedBeamformerTemplate  # noqa: F401
 from .incoherent import IncoherentBeam, IncoherentBeamTemplate  # noqa: F401
 from .matrix_multiply import MatrixMultiply, MatrixMultiplyTemplate  # noqa: F401
+from .pulse_search import PulseSearch, PulseSearchTemplate, candidates  # noqa: F401
 from .prebeamform_reorder import PreBeamformReorder, PreBeamformReorderTemplate  # noqa: F401
 from .requant import Requant, RequantTemplate  # noqa: F401
 from .streaming import StreamingBeamformer, StreamingBeamformerTemplate  # noqa: F401

@@ -41,10 +41,12 @@ const char* bf_last_error(void);
  * "beam_detect" = bf_beam_detect and bf_detect_algorithmic_bytes, "voltage_stats" = bf_voltage_stats and
  * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
  * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains, "beam_streams" = bf_beam_streams and
- * bf_beam_streams_algorithmic_bytes, "dedisperse" = bf_dedisperse and bf_dedisperse_algorithmic_bytes. */
+ * bf_beam_streams_algorithmic_bytes, "dedisperse" = bf_dedisperse and bf_dedisperse_algorithmic_bytes, "pulse_search" =
+ * bf_pulse_search and bf_pulse_search_algorithmic_bytes. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan", "correlate", "check_gains", "beam_streams", "dedisperse"), 0 for any other name (and for NULL). */
+ * "fused_plan", "correlate", "check_gains", "beam_streams", "dedisperse", "pulse_search"), 0 for any other name (and for
+ * NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -72,6 +74,8 @@ const char* bf_last_kernel(void);
  *   bf_correlate                      raw 16, out 4
  *   bf_beam_streams                   beams 16, beam_index 4 (or NULL), out 16
  *   bf_dedisperse                     power 16, ring 16, lags 4, out 16
+ *   bf_pulse_search                   series 16, ring 16, moments 16, snr 16 and width_index 4 (or both NULL), peaks 16,
+ *                                     best 16; widths is host memory (none)
  *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -455,6 +459,59 @@ double bf_beam_streams_algorithmic_bytes(int B, int C, int T, int M, int K, int 
 int bf_dedisperse(const float* power, float* ring, const int32_t* lags, float* out, int B, int S, int plane, int K,
                   int J, int M, int D, int R, int head, float scale, void* stream);
 double bf_dedisperse_algorithmic_bytes(int B, int K, int J, int M, int D, long long span_sum);
+
+/* Pulse search (no reference counterpart): the matched filter of bf_dedisperse's output -- boxcar signal-to-noise of
+ * every (beam, trial) time series at a list of widths against a running baseline, the best width per sample, one peak
+ * record per (beam, trial) and one best record per beam.  What leaves the GPU is 16 bytes per (beam, trial) and 16 bytes
+ * per beam per call.
+ *   series  : f32 (M, D, N), exactly bf_dedisperse's out: N new samples of every (beam, trial) row
+ *   ring    : f32 (M, D, R), the caller-owned past of the series, zeroed before the first call; R a multiple of N with
+ *             R >= N + Wmax - 1; `head`, a multiple of N in [0, R), is the slot of this call's first sample
+ *   moments : f64 (M, D, P, 2), the caller-owned block moments (sum x, sum x*x) of the last P calls, zeroed before the
+ *             first call; `slot` in [0, P) is the one this call writes, `n_blocks` in [1, P] how many slots are filled
+ *             once it has (the current one included)
+ *   widths  : int32 (L) on the HOST, read before the call returns: 1 <= L <= 16, strictly ascending, 1 <= w <= 1024;
+ *             Wmax = widths[L-1]
+ *   snr, width_index : f32 and uint8 (M, D, N), written only with BF_PSEARCH_SERIES; both NULL without it
+ *   peaks   : int32 (M, D, 4);  best : int32 (M, 4)
+ * In stream order, per row (m, d):
+ *   1. ring[m][d][(head + n) % R] = series[m][d][n]                        (bits copied; nothing else in ring changes)
+ *   2. moments[m][d][slot] = (sum_n x, sum_n x*x) of the N new samples, float64 sums of the f32 values (nothing else in
+ *      moments changes); S1, S2 = the sums over all P slots of the two moments (unfilled slots are the caller's zeros);
+ *      cnt = n_blocks * N
+ *   3. s_w[n] = sum over i < w of ring[m][d][(head + n - i) mod R]                                          (float64)
+ *      num = cnt * s_w[n] - w * S1;  den = w * (cnt * S2 - S1 * S1)
+ *      snr_w[n] = den > 0 ? float32(num / sqrt(den)) : 0     (float64 sqrt and division, one round-to-nearest-even)
+ *      = (s_w - w * mean) / (sqrt(w) * sigma) over the last n_blocks blocks, the current one included.  The boxcar of
+ *      width w ENDS at sample n: the centre of the pulse is at n - (w - 1) / 2.
+ *   4. per sample the best width: the largest snr_w[n], ties to the smallest width index; the search starts from
+ *      (-inf, index 0) and compares strictly, so a NaN never wins  -> snr[m][d][n], width_index[m][d][n]
+ *   5. peaks[m][d] = { bits of the row's best snr, its n, its width index, count of n whose step-4 snr >= threshold };
+ *      larger snr wins, then the smaller width index, then the smaller n; the search starts from (-inf, n 0, index 0)
+ *      and compares strictly
+ *   6. best[m] = { bits of the beam's best snr over its D peak records, that record's d, n, width index }; ties go to
+ *      the smaller d; the search starts from (-inf, d 0, n 0, index 0)
+ * The library keeps no state: the caller advances head' = (head + N) % R, slot' = (slot + 1) % P and
+ * n_blocks' = min(n_blocks + 1, P).  Every output element is written once by one thread: no atomics, no output needs
+ * zeroing, two launches give identical bytes; `series` is never written.  A row that holds a NaN has den > 0 false, so
+ * its snr is 0 for as long as the NaN sits in its moments; other rows are unaffected.  For integer-valued series with
+ * |num| and den below 2^53 every product and sum is exact in any order and what remains is one float64 sqrt, one float64
+ * division and one conversion: the result is bit-exact.  For general f32 the float64 sums (of at most N + Wmax - 1
+ * terms) are within (terms) * 2^-53 * sum|x| each.  There is no scale argument: a scale of the series cancels.
+ * Refused with BF_ERR_ARG before any launch: a null pointer (snr and width_index: both NULL without
+ * BF_PSEARCH_SERIES, both non-NULL with it); unknown flag bits; M, D, N or R not positive; M or D above 4096; L
+ * outside 1..16; widths not strictly ascending or outside 1..1024; R % N != 0 or R < N + Wmax - 1; head not a multiple
+ * of N in [0, R); P outside 1..64; slot outside [0, P); n_blocks outside [1, P]; n_blocks * N at or above 2^31; a
+ * threshold that is not finite; series, ring, moments, snr, peaks or best not 16-byte aligned, width_index not 4-byte
+ * aligned.  All element offsets are 64-bit.
+ * bf_pulse_search_algorithmic_bytes: M*D * (4 * (2N + Wmax - 1) [the block read and appended, the history read once] +
+ * 16 * P [the moment slots] + 16 [the peak record]) + 16 * M [the best records] + 5 * M*D*N with BF_PSEARCH_SERIES; 0
+ * for any shape or flags bf_pulse_search refuses (L outside 1..16, Wmax outside L..1024, P outside 1..64 included). */
+#define BF_PSEARCH_SERIES 1  /* write snr and width_index (M, D, N) */
+int bf_pulse_search(const float* series, float* ring, double* moments, const int32_t* widths, float* snr,
+                    uint8_t* width_index, int32_t* peaks, int32_t* best, int M, int D, int N, int R, int head, int P,
+                    int slot, int n_blocks, int L, float threshold, int flags, void* stream);
+double bf_pulse_search_algorithmic_bytes(int M, int D, int N, int L, int Wmax, int P, int flags);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

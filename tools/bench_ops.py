@@ -22,6 +22,12 @@ apart, medians of `--reps` launches; each line with the K*D*N*M additions per se
 bytes, the telescope time one call covers (B*T / 208984 s) and the naive one-thread-per-output kernel
 (build/libbf_dedisperse_naive.so, `make dedisperse-naive`; step 2 only, no append) on the same ring in the same process;
 its lines also go to `--out` (profiles/dedisperse_ops.jsonl).
+`--pulse-search` runs the pulse search alone on the dedisperser's four lines (cfg3 and cfg4, 64 and 256 trials): a
+series of the dedisperser's output shape (chi-squared noise of 4096 degrees of freedom, as a sum of K channel powers
+is), the default widths 1 .. 128 and the default baseline, medians of `--reps` launches with head, slot and n_blocks
+advancing as in use; each line with the stream ceiling for its own bytes, the telescope time one call covers and,
+beside them, the dedisperser's time of the same line from `--dedisperse-profile` (profiles/dedisperse_ops.jsonl) and
+whether the two together stay under the telescope time; its lines also go to `--out` (profiles/pulse_search_ops.jsonl).
 """
 import argparse
 import ctypes
@@ -37,7 +43,7 @@ import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import _lib, accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, BeamStreamsTemplate, CoeffGeneratorTemplate,  # noqa: E402
-                                          DedisperserTemplate, dispersion_lags,
+                                          DedisperserTemplate, dispersion_lags, PulseSearchTemplate,
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
                                           PreBeamformReorderTemplate, VoltageStatsTemplate, CorrelatorTemplate)
 
@@ -406,6 +412,56 @@ def run_dedisperse(ctx, q, name, c, reps):
     del power
 
 
+def run_pulse_search(ctx, q, name, c, reps, dedisperse_profile):
+    """The pulse search over a series of the dedisperser's output shape at the configuration ((tint, fint) = (16, 1):
+    N = B * T / 16 samples per call, M beams), 64 and 256 trials, the default widths and baseline, threshold 6.  The
+    series is noise with the statistics of a sum of 4096 channel powers (mean 4096, variance 8192), so every S/N takes
+    the whole arithmetic path.  Medians of `reps` launches; the state advances from launch to launch as in use (the
+    first `baseline_blocks` launches, which fill the baseline, fall in the clock settle).  Each line carries the stream
+    ceiling for the algorithmic bytes, the telescope time of one call and the dedisperser's time of the same line."""
+    M, T, B = c["M"], c["T"], c["B"]
+    N = B * (T // 16)
+    dedisp = {}
+    if os.path.exists(dedisperse_profile):
+        for ln in open(dedisperse_profile):
+            if ln.strip():
+                d = json.loads(ln)
+                dedisp[(d["config"], d["op"])] = d["us"]
+    rng = np.random.default_rng(3)
+    for D in (64, 256):
+        tmpl = PulseSearchTemplate(ctx, M, D, N)
+        op = tmpl.instantiate(q)
+        op.ensure_all_bound()
+        op.buffer("inSeries").set(q, (4096 + np.sqrt(8192) * rng.standard_normal(tmpl.input_shape)).astype(np.float32))
+        t, t_min, t_max = median_time(q, op, reps)
+        assert op.n_blocks == tmpl.baseline_blocks  # the baseline was full while the launches were timed
+        kernel = _lib.load().bf_last_kernel().decode()
+        above = int(op.buffer("outPeaks").get(q)[..., 3].sum())
+        alg = int(tmpl.algorithmic_bytes())
+        rows = M * D
+        write_bytes = rows * (4 * N + 16 + 16) + 16 * M
+        read_bytes = alg - write_bytes
+        ring_bytes, moment_bytes = op.ring.nbytes, op.moments.nbytes
+        del op
+        ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+        telescope = B * T / SAMPLE_RATE
+        extra = {}
+        d_us = dedisp.get((name, f"dedisperse_D{D}"))
+        if d_us is not None:
+            both = d_us + t * 1e6
+            extra = dict(dedisperse_us=d_us, chain_us=round(both, 2),
+                         chain_over_telescope=round(both / telescope / 1e6, 4),
+                         chain_under_telescope=bool(both < telescope * 1e6))
+        emit(name, f"pulse_search_D{D}", t, alg, n_trials=D, n_samples=N, n_beams=M, widths=tmpl.widths.tolist(),
+             baseline_blocks=tmpl.baseline_blocks, ring_length=tmpl.ring_length, ring_bytes=ring_bytes,
+             moment_bytes=moment_bytes, threshold=tmpl.threshold, samples_above_threshold=above, reps=reps,
+             min_us=round(t_min * 1e6, 2), max_us=round(t_max * 1e6, 2), kernel=kernel, read_bytes=read_bytes,
+             write_bytes=write_bytes, readback_bytes=16 * rows + 16 * M, ceiling_us=round(ct * 1e6, 2),
+             ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+             ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4),
+             telescope_us=round(telescope * 1e6, 1), times_real_time=round(telescope / t, 1), **extra)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -421,23 +477,31 @@ def main():
                    "bf_reorder on a cube of the same byte count")
     p.add_argument("--dedisperse", action="store_true", help="only the dedisperser, its stream ceiling and the naive "
                    "kernel on the same ring")
-    p.add_argument("--out", default=None, help="--correlate, --beam-streams, --dedisperse: the file that receives the "
-                   "lines as well (profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl, "
-                   "profiles/dedisperse_ops.jsonl)")
+    p.add_argument("--pulse-search", action="store_true", help="only the pulse search, its stream ceiling and the "
+                   "dedisperser's recorded time of the same line")
+    p.add_argument("--dedisperse-profile", default=os.path.join(ROOT, "profiles", "dedisperse_ops.jsonl"),
+                   help="--pulse-search: the dedisperser's lines (the output of --dedisperse)")
+    p.add_argument("--out", default=None, help="--correlate, --beam-streams, --dedisperse, --pulse-search: the file that "
+                   "receives the lines as well (profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl, "
+                   "profiles/dedisperse_ops.jsonl, profiles/pulse_search_ops.jsonl)")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
-    if args.correlate or args.beam_streams or args.dedisperse:
+    if args.correlate or args.beam_streams or args.dedisperse or args.pulse_search:
         global EMIT_FILE
         default = ("correlate_ops.jsonl" if args.correlate else
-                   "beam_streams_ops.jsonl" if args.beam_streams else "dedisperse_ops.jsonl")
+                   "beam_streams_ops.jsonl" if args.beam_streams else
+                   "dedisperse_ops.jsonl" if args.dedisperse else "pulse_search_ops.jsonl")
         EMIT_FILE = open(args.out or os.path.join(ROOT, "profiles", default), "w")
     for name in args.only.split(","):
-        if args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams or args.dedisperse:
+        if (args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams or args.dedisperse or
+                args.pulse_search):
             if name in DEDISPERSE_CONFIGS and args.dedisperse:
                 run_dedisperse(ctx, q, name, CONFIGS[name], args.reps)
+            if name in DEDISPERSE_CONFIGS and args.pulse_search:
+                run_pulse_search(ctx, q, name, CONFIGS[name], args.reps, args.dedisperse_profile)
             if name in INCOHERENT_CONFIGS and args.beam_streams:
                 run_beam_streams(ctx, q, name, CONFIGS[name], args.reps)
             if name in CORRELATE_CONFIGS and args.correlate:
