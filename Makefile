@@ -9,11 +9,11 @@ SRCS     := $(CSRC)/bf_runtime.cpp $(CSRC)/bf_coeff.hip $(CSRC)/bf_reorder.hip $
             $(CSRC)/bf_fused.hip $(CSRC)/bf_wide.hip $(CSRC)/bf_wide_i8.hip $(CSRC)/bf_q14table.hip $(CSRC)/bf_requant.hip \
             $(CSRC)/bf_study.hip $(CSRC)/bf_incoherent.hip $(CSRC)/bf_detect.hip $(CSRC)/bf_vstats.hip \
             $(CSRC)/bf_correlate.hip $(CSRC)/bf_beam_streams.hip $(CSRC)/bf_dedisperse.hip $(CSRC)/bf_pulse_search.hip \
-            $(CSRC)/bf_pipeline.cpp $(CSRC)/bf_comm.cpp $(CSRC)/bf_fused_plan.cpp
+            $(CSRC)/bf_fold.hip $(CSRC)/bf_pipeline.cpp $(CSRC)/bf_comm.cpp $(CSRC)/bf_fused_plan.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.hpp) include/bf.h
 
-.PHONY: all clean cabi stream dedisperse-naive
+.PHONY: all clean cabi stream dedisperse-naive fold-naive
 all: $(LIB) cabi
 
 # bench.py's stream ceiling (the box's best plain stream over a kernel's byte mix): a small measurement library of its
@@ -29,6 +29,14 @@ $(STREAM_LIB): tools/stream_ceiling.hip tools/stream_kernels.hpp
 NAIVE_LIB := build/libbf_dedisperse_naive.so
 dedisperse-naive: $(NAIVE_LIB)
 $(NAIVE_LIB): tools/dedisperse_naive.hip
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+
+# tools/bench_ops.py --fold: the one-thread-per-(fold, plane, channel) fold the product kernel is measured against; a
+# measurement library of its own, never linked into the product.
+FOLD_NAIVE_LIB := build/libbf_fold_naive.so
+fold-naive: $(FOLD_NAIVE_LIB)
+$(FOLD_NAIVE_LIB): tools/fold_naive.hip
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 

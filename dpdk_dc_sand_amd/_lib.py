@@ -105,6 +105,9 @@ PROTOTYPES = {
     "bf_pulse_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "bf_pulse_search_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "bf_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                        c_int, c_int, c_int, c_void_p]),
+    "bf_fold_algorithmic_bytes": (c_double, [c_int, c_int, c_int, c_int, c_int, c_int, c_longlong]),
     "bf_comm_unique_id": (c_int, [c_void_p, c_size_t]),
     "bf_comm_create": (c_int, [P_void, c_void_p, c_size_t, c_int, c_int]),
     "bf_comm_destroy": (c_int, [c_void_p]),

@@ -21,7 +21,10 @@ any subset; the int8 streams bind to VoltageStats, Correlator and IncoherentBeam
 beamforming.dedisperse -> DedisperserTemplate / Dedisperser (DM-trial time series (M, D, N) of one Stokes plane of
 BeamDetector.outData over a device ring of the recent past; dispersion_lags makes the lag table),
 beamforming.pulse_search -> PulseSearchTemplate / PulseSearch (boxcar S/N of Dedisperser.outData against a running
-baseline: one peak record per (beam, trial) and one best record per beam; candidates decodes the read-back peaks).
+baseline: one peak record per (beam, trial) and one best record per beam; candidates decodes the read-back peaks),
+beamforming.fold -> FolderTemplate / Folder (pulsar profiles (fold, Stokes, channel, bin) of BeamDetector.outData for
+known periods and dispersion measures, accumulated on the device in fixed-point phase; fold_phase_step and
+fold_channel_phases make the phase step and the per-channel phase offsets, mean_profile divides by the hits).
 The CPU reference helpers the reference tests import (beamforming/reorder.py, unit_test/*_cpu.py) live in the
 repository's `oracle/` package, which the product path never imports.
 """
@@ -33,6 +36,8 @@ from .correlate import (Correlator, CorrelatorTemplate, baseline_index, n_baseli
                         visibility_matrix)
 from .dedisperse import Dedisperser, DedisperserTemplate, dispersion_lags  # noqa: F401
 from .detect import BeamDetector, BeamDetectorTemplate  # noqa: F401
+from .fold import (Folder, FolderTemplate, fold_channel_phases, fold_phase_step,  # noqa: F401
+                   mean_profile)
 from .fused import FusedBeamformer, FusedBeamformerTemplate  # noqa: F401
 from .incoherent import IncoherentBeam, IncoherentBeamTemplate  # noqa: F401
 from .matrix_multiply import MatrixMultiply, MatrixMultiplyTemplate  # noqa: F401

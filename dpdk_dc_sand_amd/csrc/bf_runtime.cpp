@@ -101,7 +101,7 @@ int bf_abi_version(void) { return 302; }
 
 int bf_has_feature(const char* name) {
   for (const char* f : {"incoherent_beam", "beam_detect", "voltage_stats", "last_kernel", "fused_plan", "correlate",
-                        "check_gains", "beam_streams", "dedisperse", "pulse_search"})
+                        "check_gains", "beam_streams", "dedisperse", "pulse_search", "fold"})
     if (name && std::strcmp(name, f) == 0) return 1;
   return 0;
 }

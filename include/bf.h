@@ -42,11 +42,11 @@ const char* bf_last_error(void);
  * bf_vstats_algorithmic_bytes, "last_kernel" = bf_last_kernel, "fused_plan" = bf_fused_plan, "correlate" =
  * bf_correlate and bf_correlate_algorithmic_bytes, "check_gains" = bf_check_gains, "beam_streams" = bf_beam_streams and
  * bf_beam_streams_algorithmic_bytes, "dedisperse" = bf_dedisperse and bf_dedisperse_algorithmic_bytes, "pulse_search" =
- * bf_pulse_search and bf_pulse_search_algorithmic_bytes. */
+ * bf_pulse_search and bf_pulse_search_algorithmic_bytes, "fold" = bf_fold and bf_fold_algorithmic_bytes. */
 int bf_abi_version(void);
 /* 1 when this library has the named feature ("incoherent_beam", "beam_detect", "voltage_stats", "last_kernel",
- * "fused_plan", "correlate", "check_gains", "beam_streams", "dedisperse", "pulse_search"), 0 for any other name (and for
- * NULL). */
+ * "fused_plan", "correlate", "check_gains", "beam_streams", "dedisperse", "pulse_search", "fold"), 0 for any other name
+ * (and for NULL). */
 int bf_has_feature(const char* name);
 /* Thread-local name of the kernel that the last successful compute entry point on this thread launched, "" before any
  * launch; a failing call leaves it unchanged.  Where the library picks among several forms of a kernel at run time the
@@ -76,6 +76,7 @@ const char* bf_last_kernel(void);
  *   bf_dedisperse                     power 16, ring 16, lags 4, out 16
  *   bf_pulse_search                   series 16, ring 16, moments 16, snr 16 and width_index 4 (or both NULL), peaks 16,
  *                                     best 16; widths is host memory (none)
+ *   bf_fold                           power 16, chan 8, profile 8, hits 4; beam, phase0 and dphase are host memory (none)
  *   bf_fill_random                    dst 16 */
 
 /* ---- runtime helpers (device memory, streams, events) -------------------------------------------------
@@ -512,6 +513,45 @@ int bf_pulse_search(const float* series, float* ring, double* moments, const int
                     uint8_t* width_index, int32_t* peaks, int32_t* best, int M, int D, int N, int R, int head, int P,
                     int slot, int n_blocks, int L, float threshold, int flags, void* stream);
 double bf_pulse_search_algorithmic_bytes(int M, int D, int N, int L, int Wmax, int P, int flags);
+
+/* Folder (no reference counterpart): pulsar profiles of bf_beam_detect's output.  For a pulsar of known period and
+ * dispersion measure every sample of every channel is added into the phase bin its rotational phase falls in, with the
+ * channel's dispersive delay taken out; what accumulates is a (plane, channel, bin) profile per fold.  A fold is a beam,
+ * a phase and a phase step; several folds may name the same beam (several pulsars in one beam).
+ *   power   : f32 (B, S, K, J, M), exactly bf_beam_detect's out; all S planes are folded.  N = B*J samples per channel
+ *             and beam, time index n = b*J + j
+ *   beam    : int32 (F) on the HOST, read before the call returns: 0 <= beam[f] < M, repeats and any order allowed
+ *   phase0  : uint64 (F) on the HOST: the phase of sample n = 0, in turns * 2^64
+ *   dphase  : uint64 (F) on the HOST: the phase step per sample, in turns * 2^64
+ *   chan    : uint64 (F, K) on the device: the per-channel phase offset (the dispersive delay in turns), subtracted
+ *   profile : f64 (F, S, K, nbin) on the device, caller-owned accumulators, zeroed by the caller before the first call
+ *   hits    : uint32 (F, K, nbin) on the device, caller-owned, zeroed likewise
+ *   phi(f,k,n) = phase0[f] - chan[f][k] + n * dphase[f]                     (uint64, wraps mod 2^64)
+ *   bin        = ((phi >> 32) * nbin) >> 32                                 (integers only; always < nbin)
+ *   profile[f][s][k][bin] += float64(power[b][s][k][j][beam[f]])            for every s
+ *   hits[f][k][bin]       += 1
+ * The phase is fixed-point so that the binning is exact and modular: it is what NumPy's uint64 arithmetic gives, no
+ * floating-point contraction can move a sample to another bin, and a caller that advances phase0' = phase0 + N * dphase
+ * (mod 2^64) continues the fold exactly.  The library keeps no state.
+ *   1. Deterministic: two launches on equal inputs give equal bytes; no atomics; the updates of an accumulator element
+ *      are ordered, and the order of the float64 additions is the kernel's own and fixed.
+ *   2. If the power is integer-valued f32 and the accumulators stay below 2^53, profile is bit-exact; hits is always
+ *      exact (mod 2^32).
+ *   3. For general f32 an element is within t * 2^-53 * (|pre| + sum|x|) of the exact value: t its hit count in this call,
+ *      pre its value before the call, sum|x| the sum of the magnitudes of the samples that fall into it.
+ *   4. An element of profile or hits that receives no sample in a call is not written: the traffic follows the samples,
+ *      not nbin.
+ * power and chan are never written.
+ * Refused with BF_ERR_ARG before any launch: a null pointer; any of B, S, K, J, M, F, nbin not positive; S > 4, M > 4096,
+ * F > 64 or nbin > 4096; N = B*J above 2^31 - 1; a beam[f] outside [0, M); power not 16-byte, chan or profile not
+ * 8-byte, hits not 4-byte aligned.  All element offsets are 64-bit (profile at F 64, S 4, K 4096, nbin 1024 is 8 GiB).
+ * bf_fold_algorithmic_bytes: touched = the number of distinct (f, k, bin) that receive a sample in the call, counted by
+ * the caller; 4*B*S*K*J*M [the block, once] + 8*F*K [chan] + touched * (16*S + 8) [the touched accumulators read and
+ * written]; 0 for any shape bf_fold refuses and for touched < 0. */
+int bf_fold(const float* power, const int32_t* beam, const uint64_t* phase0, const uint64_t* dphase,
+            const uint64_t* chan, double* profile, uint32_t* hits, int B, int S, int K, int J, int M, int F, int nbin,
+            void* stream);
+double bf_fold_algorithmic_bytes(int B, int S, int K, int J, int M, int F, long long touched);
 
 /* ---- streaming ingest --------------------------------------------------------
  * Pinned host frames -> H2D stream -> bf_beamform_fused_weighted on a compute stream -> D2H stream, over a ring of

@@ -28,6 +28,11 @@ is), the default widths 1 .. 128 and the default baseline, medians of `--reps` l
 advancing as in use; each line with the stream ceiling for its own bytes, the telescope time one call covers and,
 beside them, the dedisperser's time of the same line from `--dedisperse-profile` (profiles/dedisperse_ops.jsonl) and
 whether the two together stay under the telescope time; its lines also go to `--out` (profiles/pulse_search_ops.jsonl).
+`--fold` runs the folder alone on detector-shaped power at cfg3 and cfg4, one fold per beam, 1024 bins, Stokes I and
+IQUV, a 4.57 ms and a 0.5 s pulsar at DM 40: each line with the algorithmic bytes for the counted touched accumulators,
+the stream ceiling for those bytes in the same process, the telescope time one call covers and the naive
+one-thread-per-row kernel (build/libbf_fold_naive.so, `make fold-naive`) on the same buffers; its lines also go to
+`--out` (profiles/fold_ops.jsonl).
 """
 import argparse
 import ctypes
@@ -43,7 +48,7 @@ import numpy as np  # noqa: E402
 
 from dpdk_dc_sand_amd import _lib, accel  # noqa: E402
 from dpdk_dc_sand_amd.beamforming import (BeamDetectorTemplate, BeamStreamsTemplate, CoeffGeneratorTemplate,  # noqa: E402
-                                          DedisperserTemplate, dispersion_lags, PulseSearchTemplate,
+                                          DedisperserTemplate, dispersion_lags, FolderTemplate, PulseSearchTemplate,
                                           FusedBeamformerTemplate, IncoherentBeamTemplate, MatrixMultiplyTemplate, OpSequenceTemplate,
                                           PreBeamformReorderTemplate, VoltageStatsTemplate, CorrelatorTemplate)
 
@@ -462,6 +467,75 @@ def run_pulse_search(ctx, q, name, c, reps, dedisperse_profile):
              telescope_us=round(telescope * 1e6, 1), times_real_time=round(telescope / t, 1), **extra)
 
 
+def run_fold(ctx, q, name, c, reps):
+    """The folder over detector-shaped power of the configuration ((tint, fint) = (16, 1): K = C, J = T / 16), one fold
+    per beam (F = M), 1024 bins, 1 and 4 Stokes planes, a 4.57 ms and a 0.5 s pulsar at DM 40 over 856-1712 MHz at
+    76.6 us samples, constant power (0.747, the byte 0x3f repeated).  Medians of `reps` launches; the phases advance from
+    launch to launch as in use and the accumulators keep accumulating.  `touched`, the distinct (fold, channel, bin) of
+    a call, is counted on the host for the first timed call (it barely depends on the starting phase).  Each line
+    carries the stream ceiling for the algorithmic bytes, the telescope time of one call and the naive kernel on the
+    same buffers."""
+    M, C, T, B = c["M"], c["C"], c["T"], c["B"]
+    K, J, F, nbin, ts = C, T // 16, M, 1024, 76.6e-6
+    N = B * J
+    path = os.path.join(ROOT, "build", "libbf_fold_naive.so")
+    if not os.path.exists(path):
+        raise OSError(f"{path} not found: build it with `make fold-naive`")
+    naive = ctypes.CDLL(path)
+    V, I = ctypes.c_void_p, ctypes.c_int
+    naive.bf_fold_naive.restype = I
+    naive.bf_fold_naive.argtypes = [V] * 7 + [I] * 7 + [V]
+    freqs = 856e6 + 856e6 * np.arange(K) / K
+    for S in (1, 4):
+        power = accel.DeviceArray(ctx, (B, S, K, J, M), np.float32)
+        _lib.call("bf_memset", power.ptr, 0x3f, power.nbytes, q.handle)
+        for label, period in (("4.57ms", 4.57e-3), ("0.5s", 0.5)):
+            tmpl = FolderTemplate(ctx, B, K, J, M, nbin, [(m, 1.0 / period, 40.0) for m in range(M)], freqs, ts,
+                                  n_stokes=S)
+            op = tmpl.instantiate(q)
+            op.bind(inPower=power)
+            op()  # allocates and zeroes the accumulators, uploads the channel phases
+            q.finish()
+            with np.errstate(over="ignore"):
+                phase0 = np.array(op.phase, np.uint64)[:, None, None] - op.chan[:, :, None]
+                phi = phase0 + np.arange(N, dtype=np.uint64) * np.array(op.phase_steps(), np.uint64)[:, None, None]
+            bins = ((phi >> np.uint64(32)) * np.uint64(nbin)) >> np.uint64(32)
+            touched = int((np.diff(np.sort(bins, axis=2), axis=2) != 0).sum()) + F * K
+            del phi, bins
+            t, t_min, t_max = median_time(q, op, reps)
+            kernel = _lib.load().bf_last_kernel().decode()
+
+            def fn():
+                steps = op.phase_steps()
+                for f in range(F):
+                    op._phase0[f], op._dphase[f] = op.phase[f], steps[f]
+                st = naive.bf_fold_naive(power.ptr, op._beam, op._phase0, op._dphase, op._chan.ptr, op.profile.ptr,
+                                         op.hits.ptr, B, S, K, J, M, F, nbin, q.handle)
+                if st != 0:
+                    raise RuntimeError(f"bf_fold_naive failed: hipError_t {st}")
+                op.phase = [(p + N * d) % (1 << 64) for p, d in zip(op.phase, steps)]
+                op.samples_seen += N
+            tn, tn_min, tn_max = median_time(q, fn, reps)
+            alg = int(tmpl.algorithmic_bytes(touched))
+            write_bytes = touched * (8 * S + 4)
+            read_bytes = alg - write_bytes
+            accumulator_bytes = op.profile.nbytes + op.hits.nbytes
+            del op
+            ct, grid, code = stream_ceiling(ctx, q, read_bytes, write_bytes, reps)
+            telescope = B * T / SAMPLE_RATE
+            emit(name, f"fold_S{S}_{label}", t, alg, n_stokes=S, period_s=period, dm=40.0, n_channels=K, n_samples=N,
+                 n_beams=M, n_folds=F, n_bins=nbin, touched=touched, samples=F * K * N,
+                 accumulator_bytes=accumulator_bytes, reps=reps, min_us=round(t_min * 1e6, 2),
+                 max_us=round(t_max * 1e6, 2), kernel=kernel, read_bytes=read_bytes, write_bytes=write_bytes,
+                 ceiling_us=round(ct * 1e6, 2), ceiling_GBps=round((read_bytes + write_bytes) / ct / 1e9, 1),
+                 ceiling_kernel=f"bf_stream_ceiling grid {grid} mode {code}", frac_of_ceiling=round(ct / t, 4),
+                 telescope_us=round(telescope * 1e6, 1), times_real_time=round(telescope / t, 1),
+                 under_telescope=bool(t < telescope), naive_us=round(tn * 1e6, 2), naive_min_us=round(tn_min * 1e6, 2),
+                 naive_max_us=round(tn_max * 1e6, 2), naive_times_real_time=round(telescope / tn, 1),
+                 naive_over_product=round(tn / t, 3))
+        del power
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--reps", type=int, default=10)
@@ -479,25 +553,30 @@ def main():
                    "kernel on the same ring")
     p.add_argument("--pulse-search", action="store_true", help="only the pulse search, its stream ceiling and the "
                    "dedisperser's recorded time of the same line")
+    p.add_argument("--fold", action="store_true", help="only the folder, its stream ceiling and the naive kernel on the "
+                   "same buffers")
     p.add_argument("--dedisperse-profile", default=os.path.join(ROOT, "profiles", "dedisperse_ops.jsonl"),
                    help="--pulse-search: the dedisperser's lines (the output of --dedisperse)")
-    p.add_argument("--out", default=None, help="--correlate, --beam-streams, --dedisperse, --pulse-search: the file that "
-                   "receives the lines as well (profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl, "
-                   "profiles/dedisperse_ops.jsonl, profiles/pulse_search_ops.jsonl)")
+    p.add_argument("--out", default=None, help="--correlate, --beam-streams, --dedisperse, --pulse-search, --fold: the "
+                   "file that receives the lines as well (profiles/correlate_ops.jsonl, profiles/beam_streams_ops.jsonl, "
+                   "profiles/dedisperse_ops.jsonl, profiles/pulse_search_ops.jsonl, profiles/fold_ops.jsonl)")
     p.add_argument("--tag", default="", help="suffix for the op names (e.g. the env variant under test)")
     args = p.parse_args()
     ctx = accel.create_some_context()
     q = ctx.create_command_queue()
     rng = np.random.default_rng(0)
-    if args.correlate or args.beam_streams or args.dedisperse or args.pulse_search:
+    if args.correlate or args.beam_streams or args.dedisperse or args.pulse_search or args.fold:
         global EMIT_FILE
         default = ("correlate_ops.jsonl" if args.correlate else
                    "beam_streams_ops.jsonl" if args.beam_streams else
-                   "dedisperse_ops.jsonl" if args.dedisperse else "pulse_search_ops.jsonl")
+                   "dedisperse_ops.jsonl" if args.dedisperse else
+                   "pulse_search_ops.jsonl" if args.pulse_search else "fold_ops.jsonl")
         EMIT_FILE = open(args.out or os.path.join(ROOT, "profiles", default), "w")
     for name in args.only.split(","):
         if (args.incoherent or args.detect or args.vstats or args.correlate or args.beam_streams or args.dedisperse or
-                args.pulse_search):
+                args.pulse_search or args.fold):
+            if name in DEDISPERSE_CONFIGS and args.fold:
+                run_fold(ctx, q, name, CONFIGS[name], args.reps)
             if name in DEDISPERSE_CONFIGS and args.dedisperse:
                 run_dedisperse(ctx, q, name, CONFIGS[name], args.reps)
             if name in DEDISPERSE_CONFIGS and args.pulse_search:
