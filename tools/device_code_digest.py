@@ -8,19 +8,9 @@ import hashlib
 import os
 import re
 import sys
-from concurrent.futures import ThreadPoolExecutor
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from store_hazard_check import compile_isa  # noqa: E402
-
-
-def make_vars(root):
-    """The Makefile's simple `NAME := value` / `NAME ?= value` assignments, continuation lines joined, $(X) expanded."""
-    text = open(os.path.join(root, "Makefile")).read().replace("\\\n", " ")
-    out = {}
-    for m in re.finditer(r"^(\w+)\s*[:?]?=\s*(.*)$", text, re.M):
-        out[m.group(1)] = re.sub(r"\$\((\w+)\)", lambda v: out.get(v.group(1), ""), m.group(2)).strip()
-    return out
+from device_build import compile_all, hipflags, product_sources  # noqa: E402
 
 
 def normalise(asm):
@@ -32,10 +22,8 @@ def normalise(asm):
 
 def digest(root, keep=None):
     """[(source name, sha256 of its normalised device assembly)] in SRCS order."""
-    v = make_vars(root)
-    srcs = [s for s in v["SRCS"].split() if s.endswith(".hip")]
-    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1, 16)) as pool:
-        texts = list(pool.map(lambda s: normalise(compile_isa(os.path.join(root, s), v["HIPFLAGS"].split())), srcs))
+    srcs = product_sources(root)
+    texts = [normalise(b.asm) for b in compile_all(srcs, hipflags(root))]
     if keep:
         os.makedirs(keep, exist_ok=True)
         for s, t in zip(srcs, texts):

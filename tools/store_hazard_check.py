@@ -6,9 +6,12 @@ also the signature of round 4's unexplained w64h race.  This scans a source's de
 swap) writing a wide store's data VGPRs within `window` instructions of it.
 Also: inline-asm results that reach an MFMA operand unpadded (scan_asm_to_mfma).
 usage: python tools/store_hazard_check.py <file.hip> [window] [extra hipcc flags]"""
+import os
 import re
-import subprocess
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import device_build  # noqa: E402
 
 
 def _regs(tok):
@@ -161,12 +164,8 @@ def scan_lds_dma_ring(asm, kernel, slot_reads=("ds_read2st64_b64", "ds_read_b64"
 
 
 def compile_isa(src, flags=()):
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S",
-                        "--cuda-device-only", src, "-o", "-"] + list(flags), capture_output=True, text=True,
-                       timeout=600)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr[-2000:])
-    return r.stdout
+    """The device assembly of `src` under the Makefile's flags, then `flags`."""
+    return device_build.compile_device(src, device_build.hipflags() + list(flags)).asm
 
 
 if __name__ == "__main__":
@@ -174,5 +173,4 @@ if __name__ == "__main__":
     total, hits = scan(compile_isa(sys.argv[1], sys.argv[3:]), window)
     print(f"{total} wide stores, {len(hits)} with a VALU rewriting their data within {window} instructions")
     for fn, t, n, j in hits[:40]:
-        name = subprocess.run(["c++filt", fn], capture_output=True, text=True).stdout.strip()[:90]
-        print(f"  {name}\n    {t}\n    +{j}: {n}")
+        print(f"  {device_build.demangle(fn)[:90]}\n    {t}\n    +{j}: {n}")
