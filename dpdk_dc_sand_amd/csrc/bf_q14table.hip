@@ -209,6 +209,11 @@ int launch_q14_table(const FusedArgs& P, uint32_t* out, int layout, hipStream_t 
   BF_REQUIRE(layout != kLayoutW32H,
              "q14 table: the halved-image layout has no generator (removed with the diagnostic build)");
   Q.run = std::min(Q.run, 64);  // (the deferred-fixup mask of q14_table_kernel holds 64 channels)
+  // the kernel's stores address a run of channel blocks from its first one with 32-bit offsets (lane w * 4 plus
+  // j * words * 4 in the scalar offset, records below 2^31): beyond that range they would be dropped
+  BF_REQUIRE(4 * words * std::min<long long>(Q.run, Q.Cn) < (1LL << 31),
+             "q14 table: a run of %lld channel blocks of %lld words is beyond the generator's 32-bit store offsets",
+             std::min<long long>(Q.run, Q.Cn), words);
   const long long gx = (words + 255) / 256, gy = (Q.Cn + Q.run - 1) / Q.run;
   BF_REQUIRE(gx < (1LL << 31) && gy < 65536 && P.B < 65536, "q14 table: grid too large");
   if (P.gain)

@@ -292,7 +292,9 @@ int bf_fused_plan(int B, int C, int T, int A, int M, int delay_channels, int has
 /* The int8 path's steering coefficients (the Q14 integer contract, oracle quantise_coeffs of fused_tables):
  *   out[b][c][m][a] = (uint16)Wc | (uint32)Ws << 16, Wc = rne(2^14 * RN32(g * RN32(cos rot))), Ws the same for sin,
  *   rot the reference's float64 phase (coeff_generator_cpu.py:145-164) of channel c + C * xeng_id at
- *   dt = t0 + b * batch_dt (SURVEY A3 time extension), g = gains[m][a] (NULL = 1).  delay_vals f32 (Cd, M, A, 4). */
+ *   dt = t0 + b * batch_dt (SURVEY A3 time extension), g = gains[m][a] (NULL = 1).  delay_vals f32 (Cd, M, A, 4).
+ *   The generator addresses a run of min(C, 64) channel blocks with 32-bit offsets: 4 * M * A * min(C, 64) >= 2^31
+ *   returns BF_ERR_ARG. */
 int bf_q14_coeffs(const float* delay_vals, int delay_channels, const float* gains, uint32_t* out, int B, int C, int A,
                   int M, int Ctot, int xeng_id, double sample_period, double t0, double batch_dt, void* stream);
 

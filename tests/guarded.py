@@ -21,8 +21,9 @@ and `verdict` demands all of
     5. KERNEL  the kernel that ran (bf_last_kernel) is the one the case claims to cover.
 
 The verdict is pure NumPy over host byte arrays (tests/test_guarded_host.py runs it over NumPy stand-ins for a kernel);
-`DeviceExecutor` is the thin upload / launch / download wrapper for the GPU cases, and `fused_ws` the guarded
-bf_beamform_fused_ws call that tests/test_gpu_edges.py and tests/test_gpu_phase_domain.py share.
+`DeviceExecutor` is the thin upload / launch / download wrapper for the GPU cases, `fused_ws` the guarded
+bf_beamform_fused_ws call that tests/test_gpu_edges.py, tests/test_gpu_phase_domain.py and tests/test_gpu_plan_edges.py
+share, and `beamform` the guarded bf_beamform call of tests/test_gpu_guarded.py and tests/test_gpu_plan_edges.py.
 
 Limits: the harness never hands a kernel a pointer or size its header forbids and never depends on a fault.  An overrun
 of up to G bytes on either side of a payload lands in memory the test owns and is reported; anything that strays
@@ -206,3 +207,23 @@ def fused_ws(ex, c, raw, d, gains, out_dtype, oracle, Ctot, xeng_id, Ts, t0, bat
     y = run_case(ex, bufs, launch, lambda outs: oracle(outs["y"]), c.expect)["y"]
     assert FC.planned_name(c) == lib.load().bf_last_kernel().decode()  # the plan, asked on the host, is what ran
     return y
+
+
+def beamform(ex, A, M, NB, B, C, signed, expect, x_off, w_off=4, P=2):
+    """One guarded bf_beamform call over random samples and a random table in [-1, 1), x and w at the given offsets
+    from a 256-byte boundary, against oracle.complex_mult within the project's float tolerance.  Returns the beams."""
+    import oracle as O
+    from tolerance import assert_beams_allclose
+    rng = np.random.default_rng(A * 7 + M + NB)
+    x = rng.integers(0, 256, (B, P, C, NB, 16, A, 2), dtype=np.uint8)
+    xv = x.view(np.int8) if signed else x
+    w = rng.uniform(-1.0, 1.0, (B, P, C, 2 * A, 2 * M)).astype(np.float32)
+    bufs = [inp("x", x, x_off), inp("w", w, w_off), out("y", (B, P, C, NB, 16, 2 * M), np.float32, 16)]
+
+    def launch(p):
+        ex._lib.call("bf_beamform", p["x"], p["w"], p["y"], B, P, C, NB, A, M, int(signed), ex.queue.handle)
+
+    def oracle(outs):
+        assert_beams_allclose(outs["y"], O.complex_mult(xv, w, signed=signed), xv, w, signed=signed)
+
+    return run_case(ex, bufs, launch, oracle, expect)["y"]

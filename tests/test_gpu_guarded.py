@@ -177,20 +177,7 @@ def test_fused_i8_via_f32(ex, case, scale, exact):
 
 
 # ---- bf_beamform --------------------------------------------------------------------------------------------------------
-def beamform(ex, A, M, NB, B, C, signed, expect, x_off, w_off=4):
-    rng = np.random.default_rng(A * 7 + M + NB)
-    x = rng.integers(0, 256, (B, 2, C, NB, 16, A, 2), dtype=np.uint8)
-    xv = x.view(np.int8) if signed else x
-    w = rng.uniform(-1.0, 1.0, (B, 2, C, 2 * A, 2 * M)).astype(np.float32)
-    bufs = [gd.inp("x", x, x_off), gd.inp("w", w, w_off), gd.out("y", (B, 2, C, NB, 16, 2 * M), np.float32, 16)]
-
-    def launch(p):
-        _lib.call("bf_beamform", p["x"], p["w"], p["y"], B, 2, C, NB, A, M, int(signed), ex.queue.handle)
-
-    def oracle(outs):
-        assert_beams_allclose(outs["y"], O.complex_mult(xv, w, signed=signed), xv, w, signed=signed)
-
-    return gd.run_case(ex, bufs, launch, oracle, expect)["y"]
+beamform = gd.beamform  # the guarded bf_beamform call (shared with tests/test_gpu_plan_edges.py)
 
 
 RING, TABLE = "beamform_table_ring_kernel:", "beamform_table_kernel:"
